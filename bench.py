@@ -24,7 +24,16 @@ There is no collective in the timed region (queries are independent;
 DESIGN.md "Multi-GPU").  At N > 1 a secondary line `weak_replicated` times
 every rank on the whole split.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--feature RotatE|bias]
+A plain run sets up, warms up, times the steps and prints the result line
+(metric, value, ms_per_step, the workload and the ranks' shards).  --full adds
+everything else to that line: per-kernel times and rooflines, the secondary
+workloads (WN18RR, kinship, training steps, the EM iteration, ...), the
+N > 1 `weak_replicated` line and the CPU / reference-PyTorch baselines.
+--dump-outputs DIR writes what the last timed step returned (see
+dump_outputs) so that two builds can be compared output for output.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--feature RotatE|bias] [--full]
+                       [--dump-outputs DIR]
 """
 import argparse
 import contextlib
@@ -71,6 +80,30 @@ def build_workload(feature):
     rows = np.asarray([x for b in test_set.batches for x in b], dtype=np.int64)
     model.train_set = train_set  # for the train-mode line (not a module attribute of the reference)
     return graph, test_set, model, rows
+
+
+DUMP_ROWS = 256            # rows of the step's output written by --dump-outputs
+DUMP_BYTES = 48 << 20      # bound on the sampled score + mask files together
+
+
+def dump_outputs(out_dir, score, mask):
+    """Write what the timed step returned — forward_rows' (score (n, |E|) f32,
+    mask (n, |E|) bool) — as .npy files under out_dir.  The whole output is
+    gigabytes, so score and mask are written for a fixed sample of rows
+    (seed 0, ascending, the same rows for the same arguments):
+      sample_rows.npy   (k,)      float64  row indices of the sample
+      score.npy         (k, |E|)  float32  score[sample_rows]
+      mask.npy          (k, |E|)  float32  mask[sample_rows] as 0 / 1
+      score_row_sum.npy (n,)      float64  every row's score summed over the entities"""
+    n, E = score.shape
+    k = max(1, min(n, DUMP_ROWS, DUMP_BYTES // (8 * E)))
+    idx = np.sort(np.random.RandomState(0).choice(n, size=k, replace=False))
+    sel = torch.from_numpy(idx).to(score.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "sample_rows.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "score.npy"), score.index_select(0, sel).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "mask.npy"), mask.index_select(0, sel).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "score_row_sum.npy"), score.sum(1, dtype=torch.float64).cpu().numpy())
 
 
 def shard_rows(test_set, world, rank):
@@ -610,6 +643,12 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--feature", default="RotatE", choices=["RotatE", "bias"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the result line can hold: per-kernel "
+                         "times and rooflines, the secondary workloads, weak_replicated at N > 1 and the CPU / "
+                         "reference-PyTorch baselines (minutes; a plain run stops at the headline figures)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="threads of the CPU baseline (default: every core this process may run on)")
@@ -667,14 +706,19 @@ def main():
     if distributed:
         dist.barrier()
     torch.cuda.synchronize(dev)
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = None  # the previous step's output is released before the next step allocates its own
+        last = step()
     torch.cuda.synchronize(dev)
     if distributed:
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, last[0], last[1])
+    del last
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if distributed:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -702,6 +746,41 @@ def main():
                   "union_is_split": sorted(set(flat)) == list(range(len(test_set))),
                   "padding_batches": len(flat) - len(test_set),
                   "rows_total_with_padding": int(sum(rows_per_rank)), "rows_counted": n_split}
+
+    # the headline figures: all a plain run reports
+    out = None
+    if rank == 0:
+        out = {
+            "metric": METRIC,
+            "value": round(n_split * args.steps / elapsed, 1),
+            "unit": "queries/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "fp32",
+            "data": "synthetic",
+            "config": {"workload": "FB15k-237 test split: %d batches, %d queries, sharded over %d rank(s) by the "
+                                   "reference evaluate()'s DistributedSampler; PredictorPlus(lstm,3,16,sum)"
+                                   " + %s; rnnlogic_rules.txt (%d rules, L<=3); seeded synthetic train graph%s"
+                                   % (len(test_set), n_split, world,
+                                      "RotatE(D=1000,gamma=9)" if args.feature == "RotatE" else "bias",
+                                      model.num_rules, " and RotatE tables" if args.feature == "RotatE" else ""),
+                       "batch_size": 32, "parallelism": "dp%d (test batches sharded, KG replicated)" % world,
+                       "rows_per_rank": rows_per_rank, "batches_per_rank": len(shard), "shards": shards,
+                       "placement": shards["ranks"] if shards else [rank_info(model, dev, local, world, backend)],
+                       "process_group": backend if distributed else None},
+        }
+    if not (args.full or args.profile_only):
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # secondary at N > 1: every rank on the whole split (replicated, weak scaling)
     weak = None
@@ -945,36 +1024,14 @@ def main():
         dominant = roof if not (ground_ms > base_ms) else ground
     else:
         dominant = ground
-    out = {
-        "metric": METRIC,
-        "value": round(n_split * args.steps / elapsed, 1),
-        "unit": "queries/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "fp32",
-        "data": "synthetic",
-        "config": {"workload": "FB15k-237 test split: %d batches, %d queries, sharded over %d rank(s) by the "
-                               "reference evaluate()'s DistributedSampler; PredictorPlus(lstm,3,16,sum)"
-                               " + %s; rnnlogic_rules.txt (%d rules, L<=3); seeded synthetic train graph%s"
-                               % (len(test_set), n_split, world,
-                                  "RotatE(D=1000,gamma=9)" if args.feature == "RotatE" else "bias",
-                                  model.num_rules, " and RotatE tables" if args.feature == "RotatE" else ""),
-                   "batch_size": 32, "parallelism": "dp%d (test batches sharded, KG replicated)" % world,
-                   "rows_per_rank": rows_per_rank, "batches_per_rank": len(shard), "shards": shards,
-                   "placement": shards["ranks"] if shards else [rank_info(model, dev, local, world, backend)],
-                   "process_group": backend if distributed else None},
+    out.update({
         "roofline": dominant,
         "kernels_ms": {"rule_encoder+node_weights": round(nodes_ms, 3), "base_score": round(base_ms, 3),
                        "tail_after_base": round(tail_ms, 3), "ground+score_isolated": round(ground_ms, 3)},
         "overlap": {"rotate_chunks": n_rot, "note": "grounding on a side stream beside the RotatE chunks; each "
                     "chunk's scoring pass after its RotatE rows"} if overlapped else None,
         "roofline_grounding": ground,
-    }
+    })
     out.update(extra)
     if weak is not None:
         out["weak_replicated"] = weak

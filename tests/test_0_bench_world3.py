@@ -37,7 +37,7 @@ def test_bench_world3_shards_and_value():
     env = dict(os.environ, RNNL_BENCH_ONE_DEVICE="1", RNNL_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"),
-           "--gpus", "3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--gpus", "3", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=420)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [x for x in out.stdout.splitlines() if x.startswith("{")]

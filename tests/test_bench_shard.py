@@ -42,3 +42,28 @@ def test_shards_partition_the_split(world):
     for rank, (_, idx) in enumerate(shards):
         want = list(iter(torch.utils.data.DistributedSampler(ts, world, rank)))
         assert idx == want
+
+
+@pytest.mark.parametrize("n", [7, 1000])
+def test_dump_outputs_sample(n, tmp_path):
+    """--dump-outputs: float32 / float64 files, the same seeded rows of score
+    and mask on every call, every row's sum, and a bounded size."""
+    import bench
+    E = 37
+    g = torch.Generator().manual_seed(n)
+    score = torch.randn((n, E), generator=g)
+    mask = torch.rand((n, E), generator=g) < 0.5
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), score, mask)
+    got = {f.name: np.load(f) for f in sorted((tmp_path / "a").iterdir())}
+    assert sorted(got) == ["mask.npy", "sample_rows.npy", "score.npy", "score_row_sum.npy"]
+    for name, a in got.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(a, np.load(tmp_path / "b" / name))
+    idx = got["sample_rows.npy"].astype(np.int64)
+    assert len(idx) == min(n, bench.DUMP_ROWS) and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+    np.testing.assert_array_equal(got["score.npy"], score.numpy()[idx])
+    np.testing.assert_array_equal(got["mask.npy"], mask.numpy()[idx].astype(np.float32))
+    np.testing.assert_allclose(got["score_row_sum.npy"], score.double().sum(1).numpy(), rtol=0, atol=1e-12)
+    # the FB15k-237 output (|E| = 14541) stays under the 64 MB bound
+    assert min(bench.DUMP_ROWS, bench.DUMP_BYTES // (8 * 14541)) * 8 * 14541 + 16 * 40932 < 64e6

@@ -1,14 +1,15 @@
 """Pin the C path-counting oracle (oracle/ground_oracle.c) to the reference:
   * the golden per-rule COO counts produced by the reference's Python grounding
-  * the reference's own C++ rule_destination (oracle/_ref/libref_miner.so),
-    compiled from /root/reference/miner (skipped where that build is absent).
+  * the reference's own C++ rule_destination: its recorded outputs
+    (tests/golden/_refminer_*.npz) and, where oracle/_ref/libref_miner.so
+    has been built from the reference sources, the miner itself.
 Exact integer equality throughout."""
 import os
 
 import numpy as np
 import pytest
 
-from conftest import ALL_CASES
+from conftest import ALL_CASES, GOLDEN
 from oracle import ground_c
 from oracle import reference_np as ref
 
@@ -61,32 +62,42 @@ def test_c_oracle_matches_golden_counts(case, fixtures):
             np.testing.assert_array_equal(f, want[b][2])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/miner") and not os.path.exists(ground_c.REF_LIB),
-                    reason="reference miner build unavailable")
 @pytest.mark.parametrize("case", ["umls_lstm_sum_bias", "kinship_lstm_sum_none", "fb_lstm_sum_bias"])
 def test_c_oracle_matches_reference_miner(case, fixtures):
+    """Against the reference miner's recorded rule_destination outputs
+    (tests/golden/_refminer_<case>.npz, tools/make_golden_refminer.py: 12
+    seeded train triples, each removed from the graph for its own query), and,
+    where the reference miner build exists, against the miner itself."""
     fx = fixtures(case)
     g, orc, rules = setup(fx)
-    miner = ground_c.RefMiner(fx.dataset_path())
-    rng = np.random.RandomState(3)
+    z = np.load(os.path.join(GOLDEN, "_refminer_%s.npz" % case), allow_pickle=False)
     facts = np.asarray(g.train_facts)
-    qs = facts[rng.choice(len(facts), 12, replace=False)]
+    qs = facts[np.random.RandomState(3).choice(len(facts), 12, replace=False)]
+    np.testing.assert_array_equal(z["q"], qs)
+    miner = ground_c.RefMiner(fx.dataset_path()) if os.path.exists(ground_c.REF_LIB) else None
     try:
-        for h, r, t in qs.tolist():
+        for k, (h, r, t) in enumerate(qs.tolist()):
+            lo, hi = int(z["ptr"][k]), int(z["ptr"][k + 1])
+            rec = list(zip(z["rid"][lo:hi].tolist(), z["dest"][lo:hi].tolist(), z["count"][lo:hi].tolist()))
+            if miner is not None:
+                live = []
+                for rid, (hd, body) in rules.relation2rules[r]:
+                    d, cnt = miner.rule_destination(h, body, (h, r, t))
+                    live += [(rid, e, c) for e, c in zip(d.tolist(), cnt.tolist())]
+                assert live == rec
             acc = {}
-            for rid, (hd, body) in rules.relation2rules[r]:
-                d, cnt = miner.rule_destination(h, body, (h, r, t))
+            for rid, e, c in rec:
                 m = ground_c.mix64(rid)
-                for e, c in zip(d.tolist(), cnt.tolist()):
-                    s, f = acc.get(e, (0, 0))
-                    acc[e] = (s + c, (f + c * m) & 0xFFFFFFFFFFFFFFFF)
+                s, f = acc.get(e, (0, 0))
+                acc[e] = (s + c, (f + c * m) & 0xFFFFFFFFFFFFFFFF)
             tt, ss, ff = orc.candidates(h, r, h, t)
             keys = sorted(acc)
             np.testing.assert_array_equal(tt, keys)
             np.testing.assert_array_equal(ss, [acc[x][0] for x in keys])
             np.testing.assert_array_equal(ff, np.asarray([acc[x][1] for x in keys], np.uint64))
     finally:
-        miner.close()
+        if miner is not None:
+            miner.close()
 
 
 def test_c_oracle_digest_consistency(fixtures):

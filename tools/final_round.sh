@@ -15,9 +15,8 @@ tail -2 gpurun_out/$tag/build_on_box.log
 NO_BENCH=1 bash tools/gpu_check.sh $tag || exit 1
 bash tools/profile_round.sh $tag > gpurun_out/prof_$tag.log 2>&1 || { tail -5 gpurun_out/prof_$tag.log; exit 1; }
 tail -2 gpurun_out/prof_$tag.log | cut -c1-200
-# the default bench line, reading traffic summaries stamped with these kernel sources
+# the bench.py --full line, reading traffic summaries stamped with these kernel sources
 cp gpurun_out/prof_$tag/traffic_rotate.json gpurun_out/prof_$tag/traffic_bias.json profiles/
-timeout -k 10 600 python -u bench.py > gpurun_out/$tag/bench.json 2> gpurun_out/$tag/bench.err || { tail -30 gpurun_out/$tag/bench.err; exit 1; }
-cut -c1-400 gpurun_out/$tag/bench.json
+ONLY_BENCH=1 bash tools/gpu_check.sh $tag | cut -c1-400 || exit 1
 bash tools/pmc_valu.sh || exit 1
 echo final round pass done
