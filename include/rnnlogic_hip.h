@@ -324,6 +324,10 @@ int rnnl_debug_sort_bits(int32_t bits);
  * reused between candidates with equal bucket entries) off (0) or on (1,
  * the default), so that a test can compare the outputs both ways. */
 int rnnl_debug_pair_memo(int32_t on);
+/* Test / A-B hook: rnnl_predictorplus_forward_rotate computes duplicate
+ * (h, r) eval rows once in launches of at least min_rows rows (0: never,
+ * -1: the default, 512).  Outputs do not depend on it. */
+int rnnl_debug_dedupe(int32_t min_rows);
 
 /* ------------------------------------------------------- EM Predictor --
  * The EM loop's rule-weight predictor (reference src/predictors.py:17-119,
@@ -452,7 +456,18 @@ int rnnl_rotate_score_pieces(const float *eemb, const void *entity_table, const 
  * host thread and device).
  * events (nullable, 3 hipEvent_t, each nullable): recorded on `stream` before
  * the launches, after RotatE and the mask, and after the side stream's work
- * (timing).  Same scores as the one-stream path, bit for bit. */
+ * (timing).  Same scores as the one-stream path, bit for bit.
+ * Duplicate rows: an eval-mode row's outputs depend on its (h, r) alone.  In a
+ * launch without edges_to_remove and digest, outside stream capture and of at
+ * least 512 rows (rnnl_debug_dedupe), the distinct (h, r) keys are found on
+ * the device first (their count is read back with a wait on a side stream
+ * only), every kernel above runs on those rows and writes each key's result
+ * into its first row of score, and a last kernel on `stream` copies the rows
+ * and candidate counts to the duplicates — the same score, mask and n_cand,
+ * bit for bit, in the caller's row order; no second score matrix.  The row
+ * plan lives in the workspace (rnnl_forward_workspace_size includes it:
+ * 52 to 76 bytes per row).  totals then count the distinct rows' candidates
+ * and entries.  A launch whose rows are all distinct runs as before. */
 typedef struct {
   const float *eemb;       /* RotatE.eemb (n_entities x 2 dim) */
   const void *etab;        /* rnnl_rotate_entity_table */

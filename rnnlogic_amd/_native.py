@@ -86,6 +86,7 @@ SIGNATURES = [
     ("rnnl_debug_capacity", ctypes.c_int, [_I64, _I64, _I64]),
     ("rnnl_debug_sort_bits", ctypes.c_int, [_I32]),
     ("rnnl_debug_pair_memo", ctypes.c_int, [_I32]),
+    ("rnnl_debug_dedupe", ctypes.c_int, [_I32]),
     ("rnnl_fill_rows", ctypes.c_int, [_P, _I32, _I32, _P, _P]),
     ("rnnl_fill_value", ctypes.c_int, [_F32, _I64, _P, _P]),
     ("rnnl_rotate_table_sizes", ctypes.c_int, [_I32, _I32, _I32, _I32, _P, _P]),

@@ -42,6 +42,7 @@ constexpr int WG_PER_CU = 2;           // grounding workgroups per CU at SOLO_GB
 constexpr int NUM_CU = 256;
 constexpr int SCORE_WG_PER_CU = 8;     // scoring workgroups per CU (full grid)
 constexpr int EMPTY = -1;
+constexpr int PLAN_BS = 256;  // threads per workgroup of the row-plan kernels
 constexpr int WIDE_ROWS = 256;  // launches of at most this many rows ground with 1024-lane workgroups
 // Phase-B hash passes rank their candidates by entity through an LDS bitmap
 // over the pass's entity range (it shares phase A's per-thread arrays, 36 B
@@ -117,6 +118,9 @@ struct KParams {
   float *q_scale;    // per query: PNA mean log-degree
   const int32_t *order;  // nullable: the grounding's dequeue order (heaviest estimated queries first)
   int32_t atomic_out;  // deferred scoring into a zeroed score matrix: atomic adds
+  // nullable: the score row of query q (the rows of a launch are the distinct
+  // (h, r) keys of the caller's rows, each written into its first row: Plan)
+  const int32_t *row_of;
   int4 *cand;        // per pool index: candidate record (entity, bucket start, bucket length, 0)
                      // (the first n_cand entries of a query's run)
   int2 *bent;        // bucket entries: (trie node, path count bits)
@@ -141,6 +145,11 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
 }
 
 __device__ __forceinline__ uint32_t hash32(uint32_t k) { return k * 2654435761u; }
+
+// Element (q, t) of the score matrix (KParams::row_of)
+__device__ __forceinline__ int64_t score_index(const KParams &p, int q, int t) {
+  return (int64_t)(p.row_of ? p.row_of[q] : q) * p.g.E + t;
+}
 
 // Per-slot scratch: two frontier buffers and the contribution list, each an
 // array of 8-B entries (key, count) — one contiguous run per list, so a query
@@ -181,6 +190,27 @@ struct Layout {
   int64_t nslots, fcap, pcap, pool_cap;
   int64_t off_qbase, off_qscale, off_order, off_cand, off_bent, off_slots, off_chunk, chunk_cap, off_memo, off_ptab, ptab_bits,
       total;
+  // the row plan of a launch that computes duplicate (h, r) rows once (Plan)
+  int64_t off_plan_hdr, off_rowof, off_inv, off_uh, off_ur, off_ncand, off_blk, off_hkey, off_hrow, hbits;
+};
+
+// Row plan (rnnl_predictorplus_forward_rotate, eval rows): the distinct
+// (h, r) keys of the nq rows in first-occurrence order.  row_of[u] is the
+// smallest row holding key u, inv[i] the key index of row i, uh / ur the
+// compact rows the forward runs on, n_cand their candidate counts; the
+// header holds nu.  hkey / hrow: the open-addressing table the plan is built
+// with (2^hbits >= 2 nq slots).  The plan lies behind every other buffer, so
+// the forward over nu <= nq rows (whose own layout is no larger) never
+// reaches it.
+struct Plan {
+  int32_t nq, hbits;
+  const int64_t *all_h, *all_r;
+  int64_t E;
+  unsigned int *hdr;  // [0] nu
+  int32_t *row_of, *inv, *n_cand, *blk;
+  int64_t *uh, *ur;
+  unsigned long long *hkey;
+  unsigned int *hrow;
 };
 
 inline int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
@@ -223,6 +253,29 @@ inline Layout make_layout(int64_t nq, int64_t scale, int64_t n_nodes = 0) {
   while (L.ptab_bits < 23 && (1ll << L.ptab_bits) < 128 * std::max<int64_t>(nq, 1)) ++L.ptab_bits;
   L.off_ptab = o = align256(o);
   if (n_nodes > 0) o += 8ll << L.ptab_bits;
+  {
+    const int64_t n = std::max<int64_t>(nq, 1);
+    L.off_plan_hdr = o = align256(o);
+    o += 256;
+    L.off_rowof = o = align256(o);
+    o += 4 * n;
+    L.off_inv = o = align256(o);
+    o += 4 * n;
+    L.off_uh = o = align256(o);
+    o += 8 * n;
+    L.off_ur = o = align256(o);
+    o += 8 * n;
+    L.off_ncand = o = align256(o);
+    o += 4 * n;
+    L.off_blk = o = align256(o);
+    o += 4 * (n / PLAN_BS + 2);
+    L.hbits = 4;
+    while ((1ll << L.hbits) < 2 * n) ++L.hbits;
+    L.off_hkey = o = align256(o);
+    o += 8ll << L.hbits;
+    L.off_hrow = o = align256(o);
+    o += 4ll << L.hbits;
+  }
   L.total = o;
   return L;
 }
@@ -358,5 +411,7 @@ int setup_params(const char *who, rnnl_graph g, rnnl_rules r, const int64_t *all
 void set_score_params(KParams &p, const rnnl_predictor_params *pp, float *score, uint8_t *mask, uint64_t *digest);
 bool bad_params(const rnnl_predictor_params *pp, const float *score);
 KParams export_params(void *ws, int32_t nq, int32_t scale, const int32_t *n_cand);  // the pool's carve-up only
+void plan_enqueue(const Plan &pl, hipStream_t st);                                        // dedupe.hip
+void replicate_enqueue(const Plan &pl, int E, float *score, int32_t *n_cand, hipStream_t st);  // dedupe.hip
 
 }  // namespace rnnl

@@ -1478,10 +1478,12 @@ int rnnl_predictorplus_ground(rnnl_graph g, rnnl_rules r, int32_t aggregator, co
   return RNNL_OK;
 }
 
-int rnnl_predictorplus_score(rnnl_graph g, rnnl_rules r, const rnnl_predictor_params *pp, const int64_t *all_h,
-                             const int64_t *all_r, int32_t nq, float *score, uint8_t *mask, int32_t *n_cand,
-                             uint64_t *digest, void *ws, size_t ws_bytes, int32_t scale, int32_t workgroups,
-                             int32_t deferred, void *stream) {
+// rnnl_predictorplus_score with a nullable map from query to score row
+// (KParams::row_of).
+static int score_rows(rnnl_graph g, rnnl_rules r, const rnnl_predictor_params *pp, const int64_t *all_h,
+                      const int64_t *all_r, int32_t nq, float *score, uint8_t *mask, int32_t *n_cand,
+                      uint64_t *digest, void *ws, size_t ws_bytes, int32_t scale, int32_t workgroups,
+                      int32_t deferred, const int32_t *row_of, void *stream) {
   if (bad_params(pp, score) || !n_cand || (deferred != 0 && deferred != 2) ||
       (deferred == 2 && (mask || pp->feature != RNNL_FEATURE_ADD))) {
     set_error("rnnl_predictorplus_score: bad arguments");
@@ -1494,10 +1496,19 @@ int rnnl_predictorplus_score(rnnl_graph g, rnnl_rules r, const rnnl_predictor_pa
   if (nq == 0) return RNNL_OK;
   set_score_params(p, pp, score, mask, digest);
   p.atomic_out = deferred == 2;
+  p.row_of = row_of;
   hipStream_t st = (hipStream_t)stream;
   launch_score(p, r->d, st, workgroups);  // (its chunk-list kernel resets the scoring dequeue counter)
   RNNL_HIP_CHECK(hipGetLastError());
   return RNNL_OK;
+}
+
+int rnnl_predictorplus_score(rnnl_graph g, rnnl_rules r, const rnnl_predictor_params *pp, const int64_t *all_h,
+                             const int64_t *all_r, int32_t nq, float *score, uint8_t *mask, int32_t *n_cand,
+                             uint64_t *digest, void *ws, size_t ws_bytes, int32_t scale, int32_t workgroups,
+                             int32_t deferred, void *stream) {
+  return score_rows(g, r, pp, all_h, all_r, nq, score, mask, n_cand, digest, ws, ws_bytes, scale, workgroups, deferred,
+                    nullptr, stream);
 }
 
 int rnnl_ground(rnnl_graph g, rnnl_rules r, const int64_t *all_h, const int64_t *all_r, const int64_t *etr,
@@ -1543,6 +1554,22 @@ int rnnl_ground_export_entries(void *ws, int32_t nq, int32_t scale, const int32_
 
 int rnnl_debug_pair_memo(int32_t on) {
   g_pair_memo = on != 0;
+  return RNNL_OK;
+}
+
+// Launches of at least this many rows compute duplicate (h, r) eval rows once
+// (rnnl_predictorplus_forward_rotate; 0: never).  Below it a launch is
+// latency-bound (a 32-row reference batch: 0.25 ms per call) and must not pay
+// the plan's mid-call wait.
+constexpr int32_t DEDUPE_MIN_ROWS = 512;
+static int32_t g_dedupe_min = DEDUPE_MIN_ROWS;
+
+int rnnl_debug_dedupe(int32_t min_rows) {
+  if (min_rows < -1) {
+    set_error("rnnl_debug_dedupe: need min_rows >= 0 (0: off), or -1 for the default");
+    return RNNL_ERR_INVALID;
+  }
+  g_dedupe_min = min_rows < 0 ? DEDUPE_MIN_ROWS : min_rows;
   return RNNL_OK;
 }
 
@@ -1730,6 +1757,47 @@ int rnnl_forward_rotate_zero(float *score, size_t n_floats, void *stream) {
   return RNNL_OK;
 }
 
+// The row plan of a launch (fwd.h Plan) in the workspace, built on side
+// stream A behind the caller's stream (the rows may still be in flight
+// there); nu = the number of distinct (h, r) keys, read back with a wait for
+// A alone.
+static int row_plan(HostSide *h, rnnl_graph g, rnnl_rules r, const int64_t *all_h, const int64_t *all_r, int32_t nq,
+                    void *ws, size_t ws_bytes, int32_t scale, hipStream_t main, Plan &pl, int32_t &nu) {
+  const Layout Ly = make_layout(nq, scale, r->d.n_nodes);
+  if ((int64_t)ws_bytes < Ly.total) {
+    set_error("rnnl_predictorplus_forward_rotate: workspace too small");
+    return RNNL_ERR_INVALID;
+  }
+  unsigned char *base = static_cast<unsigned char *>(ws);
+  pl.nq = nq;
+  pl.hbits = (int32_t)Ly.hbits;
+  pl.all_h = all_h;
+  pl.all_r = all_r;
+  pl.E = g->d.E;
+  pl.hdr = reinterpret_cast<unsigned int *>(base + Ly.off_plan_hdr);
+  pl.row_of = reinterpret_cast<int32_t *>(base + Ly.off_rowof);
+  pl.inv = reinterpret_cast<int32_t *>(base + Ly.off_inv);
+  pl.n_cand = reinterpret_cast<int32_t *>(base + Ly.off_ncand);
+  pl.blk = reinterpret_cast<int32_t *>(base + Ly.off_blk);
+  pl.uh = reinterpret_cast<int64_t *>(base + Ly.off_uh);
+  pl.ur = reinterpret_cast<int64_t *>(base + Ly.off_ur);
+  pl.hkey = reinterpret_cast<unsigned long long *>(base + Ly.off_hkey);
+  pl.hrow = reinterpret_cast<unsigned int *>(base + Ly.off_hrow);
+  unsigned int *pin_nu = h->pinned + 48;  // past the status words (STATUS_WORDS) of the 256-byte buffer
+  RNNL_HIP_CHECK(hipEventRecord(h->in, main));
+  RNNL_HIP_CHECK(hipStreamWaitEvent(h->a, h->in, 0));
+  plan_enqueue(pl, h->a);
+  RNNL_HIP_CHECK(hipGetLastError());
+  RNNL_HIP_CHECK(hipMemcpyAsync(pin_nu, pl.hdr, sizeof(unsigned int), hipMemcpyDeviceToHost, h->a));
+  RNNL_HIP_CHECK(hipStreamSynchronize(h->a));
+  nu = (int32_t)*pin_nu;
+  if (nu < 1 || nu > nq) {
+    set_error("rnnl_predictorplus_forward_rotate: bad row plan");
+    return RNNL_ERR_INTERNAL;
+  }
+  return RNNL_OK;
+}
+
 // The launches of rnnl_predictorplus_forward_rotate (everything but the
 // header read-back).  On an error the caller joins the side streams.
 static int forward_rotate_enqueue(HostSide *h, rnnl_graph g, rnnl_rules r, const rnnl_predictor_params *pp,
@@ -1737,14 +1805,16 @@ static int forward_rotate_enqueue(HostSide *h, rnnl_graph g, rnnl_rules r, const
                                   const int64_t *etr, int32_t nq, float *score, uint8_t *mask, int32_t *n_cand,
                                   uint64_t *digest, void *ws, size_t ws_bytes, int32_t scale, int32_t ground_wg,
                                   int32_t score_wg, int32_t zeroed, void *const *events, hipStream_t main,
-                                  int32_t E) {
+                                  int32_t E, int32_t nq_out, const int32_t *row_of) {
+  // all_h / all_r / n_cand: the nq rows computed; nq_out >= nq: the rows of
+  // score and mask (row_of, nullable: the score row of computed row q)
   // events[0..2] (nullable, timing): before the launches, after RotatE and the
   // mask, after the side stream's work (PredictorPlus.forward_rows `events`)
   auto mark = [&](int k) -> hipError_t {
     return events && events[k] ? hipEventRecord((hipEvent_t)events[k], main) : hipSuccess;
   };
   if (!zeroed)
-    if (int rc = rnnl_forward_rotate_zero(score, (size_t)nq * (size_t)E, main)) return rc;
+    if (int rc = rnnl_forward_rotate_zero(score, (size_t)nq_out * (size_t)E, main)) return rc;
   RNNL_HIP_CHECK(hipEventRecord(h->in, main));
   RNNL_HIP_CHECK(mark(0));
   RNNL_HIP_CHECK(hipStreamWaitEvent(h->a, h->in, 0));
@@ -1759,18 +1829,18 @@ static int forward_rotate_enqueue(HostSide *h, rnnl_graph g, rnnl_rules r, const
   // RotatE next, so that it starts while the scoring chain is still being
   // enqueued (that chain waits for the grounding on stream A anyway)
   RNNL_HIP_CHECK(hipStreamWaitEvent(main, h->zero, 0));
-  if (int rc = rnnl_rotate_score_pieces(rot->eemb, rot->etab, rot->rtab, rot->dim, rot->gamma, all_h, all_r, nq, E,
-                                        score, 2, rot->mode, rot->workspace, rot->workspace_bytes, rot->pieces,
-                                        rot->first_share, main))
+  if (int rc = rotate_score_rows(rot->eemb, rot->etab, rot->rtab, rot->dim, rot->gamma, all_h, all_r, nq, E, score, 2,
+                                 rot->mode, rot->workspace, rot->workspace_bytes, rot->pieces, rot->first_share,
+                                 row_of, main))
     return rc;
   RNNL_HIP_CHECK(mark(1));
   if (mask) {  // the all-True mask on side stream B beside RotatE (not behind it on `stream`)
-    RNNL_HIP_CHECK(hipMemsetAsync(mask, 1, (size_t)nq * (size_t)E, h->b));
+    RNNL_HIP_CHECK(hipMemsetAsync(mask, 1, (size_t)nq_out * (size_t)E, h->b));
     RNNL_HIP_CHECK(hipEventRecord(h->mask, h->b));
   }
   RNNL_HIP_CHECK(hipStreamWaitEvent(h->a, h->zero, 0));
-  if (int rc = rnnl_predictorplus_score(g, r, pp, all_h, all_r, nq, score, nullptr, n_cand, digest, ws, ws_bytes,
-                                        scale, score_wg, 2, h->a))
+  if (int rc = score_rows(g, r, pp, all_h, all_r, nq, score, nullptr, n_cand, digest, ws, ws_bytes, scale, score_wg, 2,
+                          row_of, h->a))
     return rc;
   RNNL_HIP_CHECK(hipEventRecord(h->side, h->a));
   RNNL_HIP_CHECK(hipStreamWaitEvent(main, h->side, 0));
@@ -1797,8 +1867,38 @@ int rnnl_predictorplus_forward_rotate(rnnl_graph g, rnnl_rules r, const rnnl_pre
   if (!h) return RNNL_ERR_HIP;
   hipStream_t main = (hipStream_t)stream;
   const int32_t E = rot->n_entities;
-  const int rc = forward_rotate_enqueue(h, g, r, pp, rot, all_h, all_r, etr, nq, score, mask, n_cand, digest, ws,
-                                        ws_bytes, scale, ground_wg, score_wg, zeroed, events, main, E);
+  // Eval rows (no removed edge) of a launch of g_dedupe_min rows or more: the
+  // forward runs on the distinct (h, r) keys and writes each into the key's
+  // first row; replicate_enqueue copies the rows to the duplicates (DESIGN
+  // §3.8).  Not with the test digest (per row) or under stream capture (the
+  // plan's size is read back mid-call).
+  Plan pl{};
+  int32_t nu = nq;
+  int rc = RNNL_OK;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (!etr && !digest && g_dedupe_min > 0 && nq >= g_dedupe_min && nq >= 2 && all_h && all_r && g && r &&
+      scale >= 1 && hipStreamIsCapturing(main, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
+    // the zero fill does not depend on the plan: on side stream B beside it
+    if (!zeroed) {
+      rc = rnnl_forward_rotate_zero(score, (size_t)nq * (size_t)E, main);
+      zeroed = 1;
+    }
+    if (!rc) rc = row_plan(h, g, r, all_h, all_r, nq, ws, ws_bytes, scale, main, pl, nu);
+  }
+  const bool dedupe = nu < nq;  // all rows distinct: the plain launch, no copy
+  if (!rc)
+    rc = dedupe ? forward_rotate_enqueue(h, g, r, pp, rot, pl.uh, pl.ur, nullptr, nu, score, mask, pl.n_cand, nullptr,
+                                         ws, ws_bytes, scale, ground_wg, score_wg, zeroed, events, main, E, nq,
+                                         pl.row_of)
+                : forward_rotate_enqueue(h, g, r, pp, rot, all_h, all_r, etr, nq, score, mask, n_cand, digest, ws,
+                                         ws_bytes, scale, ground_wg, score_wg, zeroed, events, main, E, nq, nullptr);
+  if (!rc && dedupe) {  // `main` has joined A and B: the representatives' rows are complete
+    replicate_enqueue(pl, E, score, n_cand, main);
+    if (hipGetLastError() != hipSuccess) {
+      set_error("rnnl_predictorplus_forward_rotate: replicate launch failed");
+      rc = RNNL_ERR_HIP;
+    }
+  }
   if (rc) {
     // a failed enqueue may leave work on side streams A / B that writes the
     // caller's buffers (score, mask, n_cand, ws): join both into `stream`

@@ -83,6 +83,13 @@ void set_error(const std::string &msg);
 // every node of the table (rnnl_lstm_encode_trie_sum's last launch).
 int node_fix_enqueue(rnnl_rules r, void *node_w, void *stream);
 
+// rnnl_rotate_score_pieces with a nullable map from query to score row
+// (rotate.hip; the forward over the distinct (h, r) keys of the caller's rows).
+int rotate_score_rows(const float *eemb, const void *etab, const float *rtab, int32_t D, float gamma,
+                      const int64_t *all_h, const int64_t *all_r, int32_t nq, int32_t E, float *score,
+                      int32_t accumulate, int32_t mode, void *workspace, size_t ws_bytes, int32_t pieces_req,
+                      float first_share, const int32_t *row_of, void *stream);
+
 }  // namespace rnnl
 
 struct rnnl_graph_s {

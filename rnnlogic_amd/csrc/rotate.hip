@@ -147,7 +147,8 @@ __global__ __launch_bounds__(256, 1) void rotate_mfma_kernel(const float *__rest
                                                           const int64_t *__restrict__ all_h,
                                                           const int64_t *__restrict__ all_r, int nq, int E,
                                                           float *__restrict__ score, int accumulate,
-                                                          unsigned long long *clk) {
+                                                          unsigned long long *clk,
+                                                          const int32_t *__restrict__ row_of) {
   __shared__ __attribute__((aligned(16))) uint2 sA[2][MDC][4][MQ];
   __shared__ __attribute__((aligned(16))) float sN[2][MDC][MQ];
   const int tid = threadIdx.x;
@@ -261,7 +262,7 @@ __global__ __launch_bounds__(256, 1) void rotate_mfma_kernel(const float *__rest
         const int q = q0 + qg * 16 + k * 4 + j;
         const int e = e_base + g * 16 + i16;
         if (q < nq && e < E) {
-          const int64_t idx = (int64_t)q * E + e;
+          const int64_t idx = (int64_t)(row_of ? row_of[q] : q) * E + e;
           const float val = gamma - acc[qg][g][j];
           if (accumulate == 2)
             unsafeAtomicAdd(score + idx, val);
@@ -323,7 +324,8 @@ static_assert(ROT_RE % 64 == 0 && 256 % ROT_RE == 0, "whole waves per query grou
 __global__ __launch_bounds__(RB) void rotate_direct_kernel(const float *__restrict__ ptab,
                                                            const float *__restrict__ hr, int D, float gamma,
                                                            int nq, int E, float *__restrict__ score,
-                                                           int accumulate, unsigned long long *clk, int64_t blk0) {
+                                                           int accumulate, unsigned long long *clk, int64_t blk0,
+                                                           const int32_t *__restrict__ row_of) {
   const int64_t Ep = ent_pad(E);
   int et, qt;
   const int ngroups = (nq + DQ - 1) / DQ;
@@ -395,7 +397,9 @@ __global__ __launch_bounds__(RB) void rotate_direct_kernel(const float *__restri
 #pragma unroll
     for (int k = 0; k < DQ; ++k) {
       if (q0 + k < nq) {
-        const int64_t idx = (int64_t)(q0 + k) * E + e;
+        // row_of (nullable): the score row of query q0 + k — a wave-uniform
+        // address, so the row offsets stay scalar loads / SGPRs
+        const int64_t idx = (int64_t)(row_of ? row_of[q0 + k] : q0 + k) * E + e;
         const float v = gamma - acc[k];
         if (accumulate == 2)  // into a zeroed matrix beside deferred scoring adds (rnnl_rotate_score)
           unsafeAtomicAdd(score + idx, v);
@@ -485,17 +489,22 @@ __global__ __launch_bounds__(RB) void rotate_split_kernel(const float *__restric
 
 __global__ __launch_bounds__(256) void rotate_combine_kernel(const float *__restrict__ parts, int nchunks, int nq,
                                                              int E, float gamma, float *__restrict__ score,
-                                                             int accumulate) {
+                                                             int accumulate, const int32_t *__restrict__ row_of) {
   const int64_t n = (int64_t)nq * E;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float acc = 0.f;
     for (int c = 0; c < nchunks; ++c) acc += parts[(int64_t)c * n + i];
     acc += parts[(int64_t)nchunks * n + i];
     const float v = gamma - acc;
+    int64_t o = i;  // the chunk sums are per query; row_of (nullable) maps the query to its score row
+    if (row_of) {
+      const int64_t q = i / E;
+      o = (int64_t)row_of[q] * E + (i - q * E);
+    }
     if (accumulate == 2)
-      unsafeAtomicAdd(score + i, v);
+      unsafeAtomicAdd(score + o, v);
     else
-      score[i] = accumulate ? score[i] + v : v;
+      score[o] = accumulate ? score[o] + v : v;
   }
 }
 
@@ -873,61 +882,8 @@ int rnnl_rotate_score_pieces(const float *eemb, const void *etab, const float *r
                              const int64_t *all_h, const int64_t *all_r, int32_t nq, int32_t E, float *score,
                              int32_t accumulate, int32_t mode, void *workspace, size_t ws_bytes, int32_t pieces_req,
                              float first_share, void *stream) {
-  if (!eemb || !etab || !rtab || !all_h || !all_r || !score || D <= 0 || E <= 0 || nq < 0 || !valid_mode(mode) ||
-      accumulate < 0 || accumulate > 2 || pieces_req < 1 || !(first_share >= 0.f && first_share < 1.f)) {
-    set_error("rnnl_rotate_score: bad arguments");
-    return RNNL_ERR_INVALID;
-  }
-  if (nq == 0) return RNNL_OK;
-  if (mode == RNNL_ROTATE_DIRECT) {
-    size_t need = 0;
-    rnnl_rotate_workspace_size(nq, E, D, mode, &need);
-    if (!workspace || ws_bytes < need) {
-      set_error("rnnl_rotate_score: workspace too small (see rnnl_rotate_workspace_size)");
-      return RNNL_ERR_INVALID;
-    }
-    hipLaunchKernelGGL(rotate_hr_kernel, dim3((unsigned)((nq + DQ - 1) / DQ), (unsigned)((D + 63) / 64)), dim3(256), 0,
-                       (hipStream_t)stream, eemb,
-                       (const float2 *)rtab, D, all_h, all_r, nq, (float *)workspace);
-    RNNL_HIP_CHECK(hipGetLastError());
-    const int groups = split_groups(nq, E, D);
-    if (groups > 1) {  // few rows: chunk sums over more blocks, then the in-order fold
-      const int nchunks = (D + DCH - 1) / DCH, cpg = (nchunks + groups - 1) / groups;
-      float *parts = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) +
-                                               (hr_bytes(nq, D) + 255) / 256 * 256);
-      const int64_t nblk = (ent_pad(E) / RB) * ((nq + DQ - 1) / DQ) * groups;
-      hipLaunchKernelGGL(rotate_split_kernel, dim3((unsigned)nblk), dim3(RB), 0, (hipStream_t)stream,
-                         (const float *)etab, (const float *)workspace, D, nq, E, cpg, parts);
-      hipLaunchKernelGGL(rotate_combine_kernel, dim3(grid_for((int64_t)nq * E)), dim3(256), 0, (hipStream_t)stream,
-                         (const float *)parts, nchunks, nq, E, gamma, score, accumulate);
-      RNNL_HIP_CHECK(hipGetLastError());
-      return RNNL_OK;
-    }
-    // pieces > 1: the grid in back-to-back launches over consecutive block
-    // ranges (the first one `first_share` of the blocks, 0 = equal pieces) —
-    // the same blocks and the same per-element arithmetic, so the scores are
-    // bitwise those of one launch.  Each launch boundary drains RotatE's
-    // waves once: side-stream workgroups that wait for registers RotatE's
-    // waves hold (the 168-VGPR PNA scoring pass) become resident there
-    // (DESIGN §3.7).
-    const int64_t total = xcd_grid(ent_pad(E) / ROT_RE, ((nq + DQ - 1) / DQ + ROT_QW - 1) / ROT_QW);
-    const float share = first_share;
-    const int pieces = (int)std::max<int64_t>(1, std::min<int64_t>(pieces_req, total / (64 * XCDS)));
-    int64_t step = (total / pieces + XCDS - 1) / XCDS * XCDS;
-    int64_t first = pieces > 1 ? (int64_t)(share * total) / XCDS * XCDS : step;
-    if (first <= 0 || first >= total) first = step;
-    if (pieces > 1 && first != step) step = ((total - first) / (pieces - 1) + XCDS - 1) / XCDS * XCDS;
-    for (int64_t b0 = 0; b0 < total; b0 += (b0 == 0 ? first : step))
-      hipLaunchKernelGGL(rotate_direct_kernel, dim3((unsigned)std::min(b0 == 0 ? first : step, total - b0)), dim3(RB),
-                         0, (hipStream_t)stream, (const float *)etab, (const float *)workspace, D, gamma, nq, E,
-                         score, accumulate, g_clk, b0);
-  } else {
-    hipLaunchKernelGGL(rotate_mfma_kernel, dim3(xcd_grid(ent_pad(E) / ME, (nq + MQ - 1) / MQ)), dim3(256), 0,
-                       (hipStream_t)stream, eemb, (const uint2 *)etab, (const float2 *)rtab, D, gamma, all_h, all_r,
-                       nq, E, score, accumulate, g_clk);
-  }
-  RNNL_HIP_CHECK(hipGetLastError());
-  return RNNL_OK;
+  return rotate_score_rows(eemb, etab, rtab, D, gamma, all_h, all_r, nq, E, score, accumulate, mode, workspace,
+                           ws_bytes, pieces_req, first_share, nullptr, stream);
 }
 
 int rnnl_rotate_backward(const float *planes, int32_t ld, const float *hr, const float *grad, int32_t nq,
@@ -1000,3 +956,74 @@ int rnnl_rotate_param_grads(const float *eemb, const float *planes, int32_t ld, 
 }
 
 }  // extern "C"
+
+// rnnl_rotate_score_pieces with the score row of every query (row_of,
+// nullable: query q's scores go to row row_of[q] — the forward over the
+// distinct (h, r) keys of the caller's rows, fwd.h Plan).  With row_of the
+// workspace may have been sized for more rows than the launch has: where it
+// cannot hold the split form's chunk sums, the one-pass kernel runs (the
+// same bits).
+int rnnl::rotate_score_rows(const float *eemb, const void *etab, const float *rtab, int32_t D, float gamma,
+                            const int64_t *all_h, const int64_t *all_r, int32_t nq, int32_t E, float *score,
+                            int32_t accumulate, int32_t mode, void *workspace, size_t ws_bytes, int32_t pieces_req,
+                            float first_share, const int32_t *row_of, void *stream) {
+  if (!eemb || !etab || !rtab || !all_h || !all_r || !score || D <= 0 || E <= 0 || nq < 0 || !valid_mode(mode) ||
+      accumulate < 0 || accumulate > 2 || pieces_req < 1 || !(first_share >= 0.f && first_share < 1.f)) {
+    set_error("rnnl_rotate_score: bad arguments");
+    return RNNL_ERR_INVALID;
+  }
+  if (nq == 0) return RNNL_OK;
+  if (mode == RNNL_ROTATE_DIRECT) {
+    size_t need = 0;
+    rnnl_rotate_workspace_size(nq, E, D, mode, &need);
+    int groups = split_groups(nq, E, D);
+    if (row_of && groups > 1 && workspace && ws_bytes < need) {
+      groups = 1;
+      need = (hr_bytes(nq, D) + 255) / 256 * 256;
+    }
+    if (!workspace || ws_bytes < need) {
+      set_error("rnnl_rotate_score: workspace too small (see rnnl_rotate_workspace_size)");
+      return RNNL_ERR_INVALID;
+    }
+    hipLaunchKernelGGL(rotate_hr_kernel, dim3((unsigned)((nq + DQ - 1) / DQ), (unsigned)((D + 63) / 64)), dim3(256), 0,
+                       (hipStream_t)stream, eemb,
+                       (const float2 *)rtab, D, all_h, all_r, nq, (float *)workspace);
+    RNNL_HIP_CHECK(hipGetLastError());
+    if (groups > 1) {  // few rows: chunk sums over more blocks, then the in-order fold
+      const int nchunks = (D + DCH - 1) / DCH, cpg = (nchunks + groups - 1) / groups;
+      float *parts = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) +
+                                               (hr_bytes(nq, D) + 255) / 256 * 256);
+      const int64_t nblk = (ent_pad(E) / RB) * ((nq + DQ - 1) / DQ) * groups;
+      hipLaunchKernelGGL(rotate_split_kernel, dim3((unsigned)nblk), dim3(RB), 0, (hipStream_t)stream,
+                         (const float *)etab, (const float *)workspace, D, nq, E, cpg, parts);
+      hipLaunchKernelGGL(rotate_combine_kernel, dim3(grid_for((int64_t)nq * E)), dim3(256), 0, (hipStream_t)stream,
+                         (const float *)parts, nchunks, nq, E, gamma, score, accumulate, row_of);
+      RNNL_HIP_CHECK(hipGetLastError());
+      return RNNL_OK;
+    }
+    // pieces > 1: the grid in back-to-back launches over consecutive block
+    // ranges (the first one `first_share` of the blocks, 0 = equal pieces) —
+    // the same blocks and the same per-element arithmetic, so the scores are
+    // bitwise those of one launch.  Each launch boundary drains RotatE's
+    // waves once: side-stream workgroups that wait for registers RotatE's
+    // waves hold (the 168-VGPR PNA scoring pass) become resident there
+    // (DESIGN §3.7).
+    const int64_t total = xcd_grid(ent_pad(E) / ROT_RE, ((nq + DQ - 1) / DQ + ROT_QW - 1) / ROT_QW);
+    const float share = first_share;
+    const int pieces = (int)std::max<int64_t>(1, std::min<int64_t>(pieces_req, total / (64 * XCDS)));
+    int64_t step = (total / pieces + XCDS - 1) / XCDS * XCDS;
+    int64_t first = pieces > 1 ? (int64_t)(share * total) / XCDS * XCDS : step;
+    if (first <= 0 || first >= total) first = step;
+    if (pieces > 1 && first != step) step = ((total - first) / (pieces - 1) + XCDS - 1) / XCDS * XCDS;
+    for (int64_t b0 = 0; b0 < total; b0 += (b0 == 0 ? first : step))
+      hipLaunchKernelGGL(rotate_direct_kernel, dim3((unsigned)std::min(b0 == 0 ? first : step, total - b0)), dim3(RB),
+                         0, (hipStream_t)stream, (const float *)etab, (const float *)workspace, D, gamma, nq, E,
+                         score, accumulate, g_clk, b0, row_of);
+  } else {
+    hipLaunchKernelGGL(rotate_mfma_kernel, dim3(xcd_grid(ent_pad(E) / ME, (nq + MQ - 1) / MQ)), dim3(256), 0,
+                       (hipStream_t)stream, eemb, (const uint2 *)etab, (const float2 *)rtab, D, gamma, all_h, all_r,
+                       nq, E, score, accumulate, g_clk, row_of);
+  }
+  RNNL_HIP_CHECK(hipGetLastError());
+  return RNNL_OK;
+}

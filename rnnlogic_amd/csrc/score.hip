@@ -491,7 +491,7 @@ __global__ __launch_bounds__(BS, 4) void score_pna_chunk_kernel(KParams p, const
     }
     if (!live) continue;
     const int te = cr.x;
-    const int64_t idx = (int64_t)q * p.g.E + te;
+    const int64_t idx = score_index(p, q, te);
     if (p.atomic_out) {  // deferred beside RotatE: added into the zeroed row (see sum_write_out)
       unsafeAtomicAdd(p.score + idx, out);
       continue;
@@ -663,7 +663,7 @@ __global__ __launch_bounds__(BS) void memo_sum_kernel(KParams p, const float *__
 }
 
 __device__ __forceinline__ void sum_write_out(const KParams &p, int q, int t, float out, float base) {
-  const int64_t idx = (int64_t)q * p.g.E + t;
+  const int64_t idx = score_index(p, q, t);
   if (p.atomic_out) {
     // deferred beside RotatE: the row starts at zero and RotatE adds its score
     // atomically too — two addends on an exact zero give fl(base + out) in
@@ -677,7 +677,7 @@ __device__ __forceinline__ void sum_write_out(const KParams &p, int q, int t, fl
 
 __device__ __forceinline__ float sum_base(const KParams &p, int q, int t) {
   if (p.feature == RNNL_FEATURE_NONE || p.atomic_out) return 0.f;
-  return p.base_row ? p.base_row[t] : p.score[(int64_t)q * p.g.E + t];
+  return p.base_row ? p.base_row[t] : p.score[score_index(p, q, t)];
 }
 
 // ---------------------------------------------------------------- pair memo

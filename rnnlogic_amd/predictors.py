@@ -1247,6 +1247,11 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         # without RotatE: the grounding on a side stream beside the rule
         # encoder (_forward_rows_fused)
         self.ground_early = True
+        # the overlapped RotatE forward computes duplicate (h, r) eval rows
+        # once in launches of at least this many rows (0: never; None: the
+        # library's default, 512 — a 32-row reference batch is latency-bound
+        # and keeps the plain launch)
+        self.native_dedupe_min = None
         # pna aggregator: RotatE in two launches (rnnl_rotate_score_pieces;
         # bitwise the same scores).  The PNA scoring pass needs ~230 registers
         # per wave and finds no room beside RotatE's waves (6 x 80 per SIMD)
@@ -1490,8 +1495,13 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         `dedupe` (eval rows only): an eval-mode row's output depends on (h, r)
         alone, so each distinct (h, r) is computed once and its row copied to
         the duplicates — bit-identical output (the FB15k-237 test split has
-        22,850 distinct (h, r) among 40,932 rows)."""
-        if dedupe and edges_to_remove is None and digest is None and events is None and all_h.numel() > 1:
+        22,850 distinct (h, r) among 40,932 rows).  The overlapped RotatE
+        forward does this natively and by default, in row order and without a
+        second score matrix (rnnl_predictorplus_forward_rotate, DESIGN §3.8;
+        `native_dedupe_min`): there the flag changes nothing."""
+        native = self.fused and self.entity_feature == "RotatE" and self.overlap
+        if dedupe and not native and edges_to_remove is None and digest is None and events is None \
+                and all_h.numel() > 1:
             key = all_r.to(torch.int64) * self.num_entities + all_h.to(torch.int64)
             uniq, inv = torch.unique(key, return_inverse=True)  # sorted by relation, then head
             if uniq.numel() < key.numel():
@@ -1656,12 +1666,16 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         while True:
             scale = self.capacity_scale
             ws = self._overlap_workspace(device, nq, scale)
+            if self.native_dedupe_min is not None:
+                _native.call("rnnl_debug_dedupe", int(self.native_dedupe_min))
             rc = _native.lib().rnnl_predictorplus_forward_rotate(
                 g, nr.ptr, ctypes.byref(params), ctypes.byref(rot), all_h.data_ptr(), all_r.data_ptr(),
                 etr.data_ptr() if etr is not None else None, nq, score.data_ptr(), mask.data_ptr(), n_cand.data_ptr(),
                 digest.data_ptr() if digest is not None else None, ws.data_ptr(), ws.numel(), scale,
                 self.overlap_ground_wg, self.overlap_score_wg, zeroed, ev, main.cuda_stream, None,
                 self._flags.ctypes.data_as(ctypes.c_void_p))
+            if self.native_dedupe_min is not None:
+                _native.call("rnnl_debug_dedupe", -1)
             if rc == _native.RNNL_ERR_OVERFLOW and self.capacity_scale < 64:
                 self.capacity_scale *= 2
                 zeroed = 0  # the retried launch starts from zeroed rows again
