@@ -19,6 +19,11 @@
 //                     a = re, b = im and m = a^2 + b^2; Ep = |E| rounded up to
 //                     256 and zero padded, so 16 lanes read 128 contiguous
 //                     bytes and never need clamping;
+//   ptab [D][2][Ep]   (direct mode) re | im planes of every entity, fp32, the
+//                     same padding.  The direct kernels read it through a
+//                     buffer descriptor rebased per 32-dim chunk (plane_chunk
+//                     / plane_load below): lane offset in one VGPR, dim offset
+//                     in the scalar offset, no per-load VALU address work;
 //   rtab [R2][D][2]   (cos, sin) of every relation phase (R2 = 2 |R|, the
 //                     second half negated, embedding.py:26).
 #include <hip/hip_runtime.h>
@@ -282,14 +287,56 @@ __global__ __launch_bounds__(256, 1) void rotate_mfma_kernel(const float *__rest
 // — per term the VALU issues exactly sub, sub, mul, fma, sqrt, add.
 // Sums are kept per DCH-dim chunk and folded into the row total, which keeps
 // the fp32 summation error of a 1000-term row near the reference's.  Entity
-// values come LCH = 2 dims at a time into fixed register slots, one block
-// ahead.  DQ = 20 / LCH = 2 measured best (75 ms vs 88 ms for 16 / 1 on the
-// FB15k-237 bench shape): more terms per dim amortise the per-dim loads and
-// address work, at 5 waves per SIMD.
+// values come LCH = 2 dims at a time, one block ahead, by buffer loads
+// (plane_load) straight into the registers the terms read: two fixed
+// register sets alternate, the loop body covering two blocks, so the loop
+// holds no VALU instruction besides the terms — 140 per two dims (100
+// v_pk_* + 40 v_sqrt_f32; 18.0 issue cycles per 64 terms), where global
+// loads with a per-lane 64-bit address and a register rotation cost 148.
+// A chunk's first dim is peeled: its chunk sum starts as the carried sqrt
+// instead of 0 + it.  DQ = 20 / LCH = 2 measured best (75 ms vs 88 ms for
+// 16 / 1 on the FB15k-237 bench shape): more terms per dim amortise the
+// per-dim loads, at 6 waves per SIMD (80 VGPRs, no scratch).
 constexpr int RB = 256;   // entities per block (one per lane)
 constexpr int DQ = 20;  // queries per block (SGPR-resident)
 constexpr int DCH = 32;   // dims per partial sum
 constexpr int LCH = 2;  // dims per entity-value prefetch block (divides DCH)
+
+// Entity-plane loads of the direct kernels (rotate_direct_kernel and
+// rotate_split_kernel share them).  ptab is read through a buffer descriptor
+// built from wave-uniform values only: the lane's address is one constant
+// byte offset (4 e, a VGPR) and the dim's plane offset rides in the
+// instruction's scalar offset, so a load costs no VALU instruction (a global
+// load forms a 64-bit per-lane address: one v_lshl_add_u64 each).  Offsets are
+// 32-bit, so the descriptor is rebased per DCH chunk: it starts at the
+// chunk's first dim and spans its DCH dims plus the LCH dims of look-ahead,
+// cut at the table's end.  That span must stay below 4 GiB
+// (plane_span_ok; rotate_score_rows refuses larger tables).  Every offset
+// formed here is inside the table by construction; a load outside the
+// descriptor's range would return 0, not fault.
+typedef __amdgpu_buffer_rsrc_t plane_rsrc;
+__host__ __device__ constexpr bool plane_span_ok(int64_t Ep) {
+  return (int64_t)(DCH + LCH) * 2 * Ep * (int64_t)sizeof(float) < ((int64_t)1 << 32);
+}
+// descriptor of the chunk that starts at dim d0 (wave-uniform arguments)
+__device__ __forceinline__ plane_rsrc plane_chunk(const float *ptab, int64_t Ep, int d0, int D) {
+  const uint32_t bytes = (uint32_t)min(DCH + LCH, D - d0) * (uint32_t)(2 * Ep) * 4u;
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ptab + (int64_t)d0 * 2 * Ep), 0, bytes, 0x00020000);
+}
+// (re, im) of the lane's entity at dim d, d0 <= d < d0 + DCH + LCH, d < D
+__device__ __forceinline__ void plane_load(plane_rsrc rs, uint32_t voff, int64_t Ep, int d0, int d, float &re,
+                                           float &im) {
+  const uint32_t so = (uint32_t)(d - d0) * (uint32_t)(2 * Ep) * 4u;  // SALU
+  re = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, so, 0));
+  im = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, so + (uint32_t)Ep * 4u, 0));
+}
+// one LCH-block starting at dim db; dims past the last one re-read dim D - 1
+// (in range, never used)
+__device__ __forceinline__ void plane_block(plane_rsrc rs, uint32_t voff, int64_t Ep, int d0, int db, int D,
+                                            float (&re)[LCH], float (&im)[LCH]) {
+#pragma unroll
+  for (int j = 0; j < LCH; ++j) plane_load(rs, voff, Ep, d0, min(db + j, D - 1), re[j], im[j]);
+}
 
 // hr[g][d][0..DQ-1 | DQ..2DQ-1] = (re | im) of (h o r)_d for queries DQ g + k.
 // One block per (query group, 64 dims): entity rows read coalesced along d,
@@ -339,52 +386,52 @@ __global__ __launch_bounds__(RB) void rotate_direct_kernel(const float *__restri
   const int e = et * ROT_RE + (int)threadIdx.x % ROT_RE;  // < Ep: the table is padded
   const int q0 = qt * DQ;
   const float *hp = hr + (int64_t)qt * D * 2 * DQ;
-  const float *ap = ptab + e;
+  const uint32_t voff = (uint32_t)e * 4;  // the lane's only address register
   // software pipeline: the sqrt of dim d runs one dim later than its
   // squared distance (a VALU result feeding v_sqrt directly costs ~6 more
   // cycles per term; tools/micro/valu_rates.hip "direct pipelined")
   float acc[DQ], sq[DQ];
 #pragma unroll
   for (int k = 0; k < DQ; ++k) acc[k] = sq[k] = 0.f;
-  // entity values: LCH dims at a time, loaded one LCH-block ahead (fixed
-  // register slots per dim, so the prefetch never waits on a rotation)
-  float va[LCH], vb[LCH], na[LCH], nb[LCH];
-#pragma unroll
-  for (int j = 0; j < LCH; ++j) {
-    const int64_t d = min(j, D - 1);
-    va[j] = ap[d * 2 * Ep];
-    vb[j] = ap[d * 2 * Ep + Ep];
-  }
+  // entity values: two fixed register sets of LCH dims each.  While the terms
+  // of one set run, the other set is loaded with the next LCH-block straight
+  // from memory (plane_load: no address arithmetic and no register rotation
+  // on the VALU), so the loop body covers two blocks.  DCH is a multiple of
+  // 2 LCH: a chunk always starts on set 0.
+  static_assert(DCH % (2 * LCH) == 0, "set parity across chunks");
+  float va[2][LCH], vb[2][LCH];
+  plane_rsrc rs = plane_chunk(ptab, Ep, 0, D);
+  plane_block(rs, voff, Ep, 0, 0, D, va[0], vb[0]);
   for (int d0 = 0; d0 < D; d0 += DCH) {
+    rs = plane_chunk(ptab, Ep, d0, D);  // rebased per chunk: SALU adds on the base
+    // the chunk sum starts as the sqrt carried in from dim d0 - 1 (0 + x == x
+    // bitwise for x >= +0: no zero fill, and the chunk's first dim has no
+    // sqrt + add of its own; sqrt(0) = 0 before the first chunk)
     float part[DQ];
 #pragma unroll
-    for (int k = 0; k < DQ; ++k) part[k] = 0.f;
-    for (int d1 = d0; d1 < min(d0 + DCH, D); d1 += LCH) {
+    for (int k = 0; k < DQ; ++k) part[k] = __builtin_amdgcn_sqrtf(sq[k]);
+    for (int d1 = d0; d1 < min(d0 + DCH, D); d1 += 2 * LCH) {
 #pragma unroll
-      for (int j = 0; j < LCH; ++j) {
-        const int64_t d = min(d1 + LCH + j, D - 1);
-        na[j] = ap[d * 2 * Ep];
-        nb[j] = ap[d * 2 * Ep + Ep];
-      }
+      for (int s = 0; s < 2; ++s) {
+        // the look-ahead past the chunk's end reads the next chunk's first
+        // block through this chunk's descriptor (it spans DCH + LCH dims)
+        plane_block(rs, voff, Ep, d0, d1 + (s + 1) * LCH, D, va[s ^ 1], vb[s ^ 1]);
 #pragma unroll
-      for (int j = 0; j < LCH; ++j) {
-        const int d = d1 + j;
-        if (d < D) {  // wave-uniform
-          const float a = va[j], b = vb[j];
-          const float *h = hp + (int64_t)d * 2 * DQ;  // wave-uniform: s_load
+        for (int j = 0; j < LCH; ++j) {
+          const int d = d1 + s * LCH + j;
+          if (d < D) {  // wave-uniform
+            const float a = va[s][j], b = vb[s][j];
+            const float *h = hp + (int64_t)d * 2 * DQ;  // wave-uniform: s_load
+            const bool first = s == 0 && j == 0 && d1 == d0;  // wave-uniform: the chunk's first trip is peeled
 #pragma unroll
-          for (int k = 0; k < DQ; ++k) {
-            part[k] += __builtin_amdgcn_sqrtf(sq[k]);  // dim d - 1 (sqrt(0) = 0 before the first)
-            const float x = h[k] - a;
-            const float y = h[DQ + k] - b;
-            sq[k] = fmaf(x, x, y * y);
+            for (int k = 0; k < DQ; ++k) {
+              if (!first) part[k] += __builtin_amdgcn_sqrtf(sq[k]);  // dim d - 1
+              const float x = h[k] - a;
+              const float y = h[DQ + k] - b;
+              sq[k] = fmaf(x, x, y * y);
+            }
           }
         }
-      }
-#pragma unroll
-      for (int j = 0; j < LCH; ++j) {
-        va[j] = na[j];
-        vb[j] = nb[j];
       }
     }
 #pragma unroll
@@ -423,7 +470,10 @@ __global__ __launch_bounds__(RB) void rotate_direct_kernel(const float *__restri
 // dim's step) and stores it; rotate_combine_kernel then folds the chunk sums
 // into the row total in chunk order and adds the last dim's sqrt — the same
 // fp32 operations in the same order, so the scores are bitwise those of
-// rotate_direct_kernel.  parts layout: [nchunks + 1][nq][E].
+// rotate_direct_kernel (whose chunk sum starts as the carried sqrt instead of
+// 0 + it: the same bits).  Entity values come through the one-pass kernel's
+// plane_chunk / plane_load, each dim's two values used at once.
+// parts layout: [nchunks + 1][nq][E].
 __global__ __launch_bounds__(RB) void rotate_split_kernel(const float *__restrict__ ptab,
                                                           const float *__restrict__ hr, int D, int nq, int E,
                                                           int chunks_per_group, float *__restrict__ parts) {
@@ -443,13 +493,14 @@ __global__ __launch_bounds__(RB) void rotate_split_kernel(const float *__restric
   const int e = et * RB + (int)threadIdx.x;  // < Ep: the table is padded
   const int q0 = qt * DQ;
   const float *hp = hr + (int64_t)qt * D * 2 * DQ;
-  const float *ap = ptab + e;
+  const uint32_t voff = (uint32_t)e * 4;
   float sq[DQ];
 #pragma unroll
   for (int k = 0; k < DQ; ++k) sq[k] = 0.f;
   if (c0 > 0) {  // the pipeline's carried value: the previous chunk's last dim
     const int d = c0 * DCH - 1;
-    const float a = ap[(int64_t)d * 2 * Ep], bb = ap[(int64_t)d * 2 * Ep + Ep];
+    float a, bb;
+    plane_load(plane_chunk(ptab, Ep, d - (DCH - 1), D), voff, Ep, d - (DCH - 1), d, a, bb);
     const float *h = hp + (int64_t)d * 2 * DQ;
 #pragma unroll
     for (int k = 0; k < DQ; ++k) {
@@ -463,8 +514,10 @@ __global__ __launch_bounds__(RB) void rotate_split_kernel(const float *__restric
     float part[DQ];
 #pragma unroll
     for (int k = 0; k < DQ; ++k) part[k] = 0.f;
+    const plane_rsrc rs = plane_chunk(ptab, Ep, c * DCH, D);
     for (int d = c * DCH; d < min(c * DCH + DCH, D); ++d) {
-      const float a = ap[(int64_t)d * 2 * Ep], bb = ap[(int64_t)d * 2 * Ep + Ep];
+      float a, bb;
+      plane_load(rs, voff, Ep, c * DCH, d, a, bb);
       const float *h = hp + (int64_t)d * 2 * DQ;  // wave-uniform: s_load
 #pragma unroll
       for (int k = 0; k < DQ; ++k) {
@@ -974,6 +1027,11 @@ int rnnl::rotate_score_rows(const float *eemb, const void *etab, const float *rt
   }
   if (nq == 0) return RNNL_OK;
   if (mode == RNNL_ROTATE_DIRECT) {
+    if (!plane_span_ok(ent_pad(E))) {  // 32-bit offsets inside one chunk's descriptor (plane_chunk)
+      set_error("rnnl_rotate_score: entity table too large for the direct kernel (one 34-dim chunk of the planes "
+                "must stay below 4 GiB: at most 15,790,080 entities)");
+      return RNNL_ERR_INVALID;
+    }
     size_t need = 0;
     rnnl_rotate_workspace_size(nq, E, D, mode, &need);
     int groups = split_groups(nq, E, D);

@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int ITERS = 4096;
 
 __device__ __forceinline__ void stamp(unsigned long long *clk, int slot) {
@@ -175,7 +176,6 @@ __global__ void k_bf16_32_sqrt(float *out, unsigned long long *clk, float x) {
   stamp(clk, 1);
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __global__ void k_pkfma(float *out, unsigned long long *clk, float x) {
   stamp(clk, 0);
   f32x2 a[8];
@@ -255,26 +255,70 @@ __global__ void k_mix(float *out, unsigned long long *clk, float x) {
 }
 
 // the direct term with the query side from s_load (wave-uniform buffer reads,
-// as rotate_direct_kernel), entity values from VGPRs
-__constant__ float c_h[64 * 32];
+// 20 rows per wave as rotate_direct_kernel's DQ).  BUF = false: entity values
+// stepped in VGPRs (72 VALU instructions per dim: the 70 of the terms, one
+// v_pk_add and one v_mov — the kernel's loop before it read the planes by
+// buffer loads carried 74: two 64-bit address adds and two rotation moves).
+// BUF = true: the kernel's loop as it is now — entity values through a buffer
+// descriptor (lane offset in a VGPR, dim offset in the scalar offset), two
+// dims per block into two alternating register sets, one block ahead; 280
+// VALU instructions per four dims: 200 v_pk_* and 80 v_sqrt_f32, nothing else.
+__constant__ float c_h[64 * 40];
+__device__ float d_ent[64 * 2 * 256];  // [dim][re | im][lane]
+template <bool BUF>
 __global__ void k_direct_sgpr(float *out, unsigned long long *clk, float x) {
   stamp(clk, 0);
-  const float *hq = c_h;  // 32 floats per iteration, uniform (s_load)
-  float acc[16], sq[16], a = x + threadIdx.x, b = x - threadIdx.x;
-  for (int j = 0; j < 16; ++j) acc[j] = sq[j] = 0;
-  for (int i = 0; i < ITERS / 2; ++i) {
-    const float *h = hq + (i & 63) * 32;
+  const float *hq = c_h;  // 40 floats per iteration (20 rows, the kernel's DQ), uniform (s_load)
+  float acc[20], sq[20], a = x + threadIdx.x, b = x - threadIdx.x;
+  for (int j = 0; j < 20; ++j) acc[j] = sq[j] = 0;
+  if (BUF) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(d_ent, 0, sizeof(d_ent), 0x00020000);
+    const unsigned voff = threadIdx.x * 4;
+    float va[2][2], vb[2][2];
+    auto load = [&](int i, float (&re)[2], float (&im)[2]) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      acc[j] += __builtin_amdgcn_sqrtf(sq[j]);
-      const float dx = h[j] - a;
-      const float dy = h[16 + j] - b;
-      sq[j] = fmaf(dx, dx, dy * dy);
+      for (int j = 0; j < 2; ++j) {
+        const unsigned so = (unsigned)((i + j) & 63) * 2048u;
+        re[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, so, 0));
+        im[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, so + 1024u, 0));
+      }
+    };
+    load(0, va[0], vb[0]);
+    const int n = (int)(x * (ITERS / 2));  // x = 1: the kernel's wave-uniform `d < D`, one basic block per dim
+    for (int i = 0; i < ITERS / 2; i += 4) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        load(i + 2 * (s + 1), va[s ^ 1], vb[s ^ 1]);
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+          if (i + 2 * s + d >= n) continue;
+          const float ea = va[s][d], eb = vb[s][d];
+          const float *h = hq + ((i + 2 * s + d) & 63) * 40;
+#pragma unroll
+          for (int j = 0; j < 20; ++j) {
+            acc[j] += __builtin_amdgcn_sqrtf(sq[j]);
+            const float dx = h[j] - ea;
+            const float dy = h[20 + j] - eb;
+            sq[j] = fmaf(dx, dx, dy * dy);
+          }
+        }
+      }
     }
-    a += 1.0f;
-    b -= 1.0f;
+  } else {
+    for (int i = 0; i < ITERS / 2; ++i) {
+      const float *h = hq + (i & 63) * 40;
+#pragma unroll
+      for (int j = 0; j < 20; ++j) {
+        acc[j] += __builtin_amdgcn_sqrtf(sq[j]);
+        const float dx = h[j] - a;
+        const float dy = h[20 + j] - b;
+        sq[j] = fmaf(dx, dx, dy * dy);
+      }
+      a += 1.0f;
+      b -= 1.0f;
+    }
   }
-  float s = 0; for (int j = 0; j < 16; ++j) s += acc[j] + sq[j];
+  float s = 0; for (int j = 0; j < 20; ++j) s += acc[j] + sq[j];
   out[blockIdx.x * blockDim.x + threadIdx.x] = s;
   stamp(clk, 1);
 }
@@ -384,8 +428,10 @@ int main() {
   printf("direct nosqrt:  %.3f ms %.2f GHz -> %.2f cyc/wave-term/SIMD\n", t, g, cyc(t, g, ITERS / 2 * 16.0));
   t = run(k_direct_pipe, out, clk, blocks, threads, &g);
   printf("direct pipelined: %.3f ms %.2f GHz -> %.2f cyc/wave-term/SIMD\n", t, g, cyc(t, g, ITERS / 2 * 16.0));
-  t = run(k_direct_sgpr, out, clk, blocks, threads, &g);
-  printf("direct sgpr-load pipelined: %.3f ms %.2f GHz -> %.2f cyc/wave-term/SIMD\n", t, g, cyc(t, g, ITERS / 2 * 16.0));
+  t = run(k_direct_sgpr<false>, out, clk, blocks, threads, &g);
+  printf("direct sgpr-load pipelined, entity values stepped on the VALU: %.3f ms %.2f GHz -> %.2f cyc/wave-term/SIMD\n", t, g, cyc(t, g, ITERS / 2 * 20.0));
+  t = run(k_direct_sgpr<true>, out, clk, blocks, threads, &g);
+  printf("direct sgpr-load pipelined, entity values by buffer loads: %.3f ms %.2f GHz -> %.2f cyc/wave-term/SIMD\n", t, g, cyc(t, g, ITERS / 2 * 20.0));
   t = run(k_mix, out, clk, blocks, threads, &g);
   printf("fma+sqrt mix:   %.3f ms %.2f GHz -> %.2f cyc/(fma+sqrt)/SIMD\n", t, g, cyc(t, g, ITERS / 2 * 16.0));
   t = run(k_sqrt, out, clk, blocks, threads, &g);
