@@ -553,6 +553,30 @@ int rnnl_filter_flags(const int64_t *keys, const int64_t *offs, const int32_t *v
 int rnnl_filtered_ranks(const float *score, const uint8_t *mask, const uint8_t *flag, const int64_t *all_t,
                         int32_t n_rows, int32_t n_entities, int64_t *L, int64_t *H, void *stream);
 
+/* Filtered top-k tail selection with a defined total order, one pass per
+ * row (no n_rows x n_entities temporary): the prediction list of (h, r, ?).
+ * score / mask / flag as for rnnl_filtered_ranks; mask, flag and keep are
+ * nullable.  In row i entity e is eligible when
+ *   mask is NULL or mask[i][e] != 0, and
+ *   flag is NULL or flag[i][e] != 0 or e == keep[i], and
+ *   score[i][e] is not NaN.
+ * keep (n_rows, nullable) re-admits one filtered entity per row — the known
+ * answer among the filtered predictions; a value outside [0, n_entities)
+ * means none; it never overrides mask or NaN.
+ * Order: score descending, then entity id ascending; -0.0 == +0.0, +-inf are
+ * ordinary values.  out_index / out_score (n_rows x k) receive the first
+ * out_valid[i] = min(k, #eligible) entities in that order (out_score is the
+ * stored float, bit for bit), the remaining slots -1 and -inf.  The result
+ * is a function of the inputs alone (no run-to-run tie order).
+ * 1 <= k <= RNNL_TOPK_MAX, n_entities >= 1, n_rows >= 0 (0: no launch);
+ * anything else is RNNL_ERR_INVALID, decided before any HIP call.  Row
+ * offsets are 64-bit (n_rows x n_entities may pass 2^31).  Asynchronous on
+ * `stream`, capture-safe. */
+#define RNNL_TOPK_MAX 1024
+int rnnl_topk_rows(const float *score, const uint8_t *mask, const uint8_t *flag, const int64_t *keep,
+                   int32_t n_rows, int32_t n_entities, int32_t k, int32_t *out_index, float *out_score,
+                   int32_t *out_valid, void *stream);
+
 /* ---------------------------------------------------------- rule mining --
  * The reference miner's RuleMiner::search (miner/rnnlogic.cpp:505-589 with
  * KnowledgeGraph::rule_search :350-382) on the GPU: for every train triple

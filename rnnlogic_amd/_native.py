@@ -19,6 +19,7 @@ FEATURE_ADD, FEATURE_NONE = 0, 1
 ROTATE_DIRECT, ROTATE_MFMA = 0, 1
 FLAG_MIXED = 1
 ERR_COUNT_WIDTH, ERR_NODE_RANGE, ERR_ACC_RANGE = 8, 16, 32
+TOPK_MAX = 1024  # RNNL_TOPK_MAX
 
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -98,6 +99,7 @@ SIGNATURES = [
      [_P, _I64, _I32, _P, _P, _P, _I64, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     ("rnnl_filter_flags", ctypes.c_int, [_P, _P, _P, _I64, _P, _I32, _I32, _P, _P]),
     ("rnnl_filtered_ranks", ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    ("rnnl_topk_rows", ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     ("rnnl_miner_create", ctypes.c_int, [_P, _I64, _I32, _I32, _P]),
     ("rnnl_miner_destroy", ctypes.c_int, [_P]),
     ("rnnl_rule_search", ctypes.c_int, [_P, _I32, _P, _I64, _P, _I64, _P, _P]),

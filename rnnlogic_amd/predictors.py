@@ -436,6 +436,143 @@ class _HipGrounding(object):
     def _needs_grad(self):
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
+    # ------------------------------------------------------------------ predictions
+    @_native.on_input_device
+    def predict_topk(self, all_h, all_r, k, flag=None, keep=None, edges_to_remove=None):
+        """The model's answers to (h, r, ?): per row the first k eligible
+        tails, score descending then entity id ascending (rnnl_topk_rows on the
+        eval forward's scores and candidate mask, one pass per row).
+
+        flag (n, |E|) bool / uint8, nullable: the filter rows (true = a ranked
+        competitor, as DeviceEvalBatches gives them); keep (n,) nullable: one
+        filtered entity per row that stays in (the known answer).  Returns
+        (index (n, k) int32, score (n, k) f32, valid (n,) int32) on the
+        device; slots past valid[i] hold -1 / -inf."""
+        with torch.no_grad():
+            score, mask = self.forward_rows(all_h, all_r, edges_to_remove)
+        return topk_rows(score, mask, flag, keep, k)
+
+    def _rules_of_node(self, device):
+        """Per trie node the rules ending at it, ascending: (ptr (n_nodes + 1,),
+        rule ids grouped by node) int64 on the device."""
+        nr = self.native_rules(device)
+        hit = getattr(nr, "rules_of_node", None)
+        if hit is None:
+            n2r = nr.node_of_rule
+            order = torch.argsort(n2r, stable=True)
+            ptr = torch.zeros(max(nr.n_nodes, 1) + 1, dtype=torch.int64, device=n2r.device)
+            torch.cumsum(torch.bincount(n2r, minlength=max(nr.n_nodes, 1)), 0, out=ptr[1:])
+            hit = nr.rules_of_node = (ptr, order)
+        return hit
+
+    @staticmethod
+    def _expand(start, length):
+        """Indices start[i] .. start[i] + length[i] of every i, concatenated,
+        and the i of each: (index, owner)."""
+        owner = torch.repeat_interleave(torch.arange(length.numel(), device=length.device), length)
+        first = torch.cumsum(length, 0) - length
+        within = torch.arange(owner.numel(), device=length.device) - first[owner]
+        return start[owner] + within, owner
+
+    @torch.no_grad()
+    @_native.on_input_device
+    def explain_rows(self, all_h, all_r, entities, edges_to_remove=None, chunk=8192):
+        """Which rules put entities[i][j] among row i's candidates: a CSR
+        (off (n m + 1,), rule (P,), count (P,)) int64 on the device whose slot
+        i m + j lists, in ascending rule id, every rule whose body reaches
+        entities[i][j] from all_h[i], with its exact path count (the
+        reference's grounding, data.py:136-173).  Rule ids index the rules as
+        set_rules read them; a -1 slot, or an entity no rule reaches, is empty;
+        duplicate rules are listed each with the count.  Built from the
+        grounding COO (ground_coo: int64 counts) in chunks of `chunk` rows."""
+        device, all_h, all_r, etr = self._rows(all_h, all_r, edges_to_remove)
+        n, E = all_h.numel(), self.graph.entity_size
+        entities = entities.to(device, torch.int64).reshape(n, -1)
+        m = entities.size(1)
+        nr = self.native_rules(device)
+        NN, NR = max(nr.n_nodes, 1), max(nr.n_rules, 1)
+        nptr, by_node = self._rules_of_node(device)
+        slots, rules, counts = [], [], []
+        for s0 in range(0, n, chunk):
+            ents = entities[s0:s0 + chunk]
+            rows = ents.size(0)
+            asked = (ents >= 0) & (ents < E)
+            if m == 0 or not bool(asked.any()):
+                continue
+            row, ent, ce, node, count = self.ground_coo(all_h[s0:s0 + chunk], all_r[s0:s0 + chunk],
+                                                        etr[s0:s0 + chunk] if etr is not None else None)
+            C = ent.numel()
+            if C == 0:
+                continue
+            cand_key = row * E + ent  # ascending: candidates are row-major by entity
+            want = (torch.arange(rows, device=device).unsqueeze(1) * E + ents)[asked]
+            slot = (torch.arange(s0, s0 + rows, device=device).unsqueeze(1) * m
+                    + torch.arange(m, device=device).unsqueeze(0))[asked]
+            c = torch.searchsorted(cand_key, want).clamp(max=C - 1)
+            hit = cand_key[c] == want
+            c, slot = c[hit], slot[hit]
+            # the entries of candidate c are ce == c, contiguous
+            n_ent = torch.bincount(ce, minlength=C)
+            e_off = torch.cumsum(n_ent, 0) - n_ent
+            pos, owner = self._expand(e_off[c], n_ent[c])
+            # a (candidate, node) pair may be split over several bucket entries: add them
+            pair, inv = torch.unique(slot[owner] * NN + node[pos], return_inverse=True)
+            total = torch.zeros(pair.numel(), dtype=torch.int64, device=device).index_add_(0, inv, count[pos])
+            p_slot, p_node = pair // NN, pair % NN
+            # every rule ending at the node gets the node's count
+            ridx, owner = self._expand(nptr[p_node], nptr[p_node + 1] - nptr[p_node])
+            r_slot, r_rule, r_count = p_slot[owner], by_node[ridx], total[owner]
+            live = r_count > 0
+            r_slot, r_rule, r_count = r_slot[live], r_rule[live], r_count[live]
+            order = torch.argsort(r_slot * NR + r_rule)
+            slots.append(r_slot[order])
+            rules.append(r_rule[order])
+            counts.append(r_count[order])
+        empty = torch.zeros(0, dtype=torch.int64, device=device)
+        slot = torch.cat(slots) if slots else empty
+        off = torch.zeros(n * m + 1, dtype=torch.int64, device=device)
+        if n * m:
+            torch.cumsum(torch.bincount(slot, minlength=n * m), 0, out=off[1:])
+        return off, (torch.cat(rules) if rules else empty), (torch.cat(counts) if counts else empty)
+
+
+def topk_rows(score, mask, flag, keep, k):
+    """rnnl_topk_rows on device tensors: score (n, E) f32, mask / flag (n, E)
+    bool or uint8 (nullable), keep (n,) integer (nullable) -> (index (n, k)
+    int32, score (n, k) f32, valid (n,) int32), on the current stream."""
+    if not score.is_cuda or score.dtype != torch.float32 or score.dim() != 2:
+        raise RuntimeError("topk_rows: score must be an (n, E) float32 tensor on a GPU")
+    device = score.device
+    n, E = score.shape
+
+    def bytes_of(x, name):
+        if x is None:
+            return None
+        if x.dtype not in (torch.bool, torch.uint8) or tuple(x.shape) != (n, E):
+            raise RuntimeError("topk_rows: %s must be an (n, E) bool / uint8 tensor" % name)
+        x = x.to(device).contiguous()
+        return x.view(torch.uint8) if x.dtype == torch.bool else x
+    score = score.contiguous()
+    mask, flag = bytes_of(mask, "mask"), bytes_of(flag, "flag")
+    if keep is not None:
+        keep = keep.to(device, torch.int64).contiguous()
+        if keep.numel() != n:
+            raise RuntimeError("topk_rows: keep must hold one entity per row")
+    k = int(k)
+    if not 1 <= k <= _native.TOPK_MAX:
+        raise ValueError("topk_rows: k must be in 1..%d, got %d" % (_native.TOPK_MAX, k))
+    index = torch.empty((n, k), dtype=torch.int32, device=device)
+    value = torch.empty((n, k), dtype=torch.float32, device=device)
+    valid = torch.empty(n, dtype=torch.int32, device=device)
+    if n == 0:
+        return index, value, valid
+    with torch.cuda.device(device):
+        _native.call("rnnl_topk_rows", score.data_ptr(), mask.data_ptr() if mask is not None else None,
+                     flag.data_ptr() if flag is not None else None, keep.data_ptr() if keep is not None else None,
+                     n, E, k, index.data_ptr(), value.data_ptr(), valid.data_ptr(),
+                     torch.cuda.current_stream(device).cuda_stream)
+    return index, value, valid
+
 
 class _RuleGrounder(_HipGrounding):
     """One rule as a one-rule trie under its head relation: the HIP grounding

@@ -403,12 +403,7 @@ class TrainerPredictor(object):
             # the device (rnnl_filter_flags), one forward over all rows
             sampler = torch_data.DistributedSampler(test_set, self.world_size, self.rank)
             torch.empty((), dtype=torch.int64).random_()  # the reference DataLoader's base-seed draw
-            if not hasattr(self, "_dev_eval"):
-                self._dev_eval = {}
-            cached = self._dev_eval.get(split)  # keyed by split, checked against the dataset object
-            if cached is None or cached.eval_set is not test_set:
-                cached = self._dev_eval[split] = DeviceEvalBatches(test_set, dev)
-            all_h, all_r, all_t, flag = cached.rows(list(iter(sampler)))
+            all_h, all_r, all_t, flag = self._device_eval_batches(split, test_set).rows(list(iter(sampler)))
             if all_h.numel():
                 logits, mask = model.forward_rows(all_h, all_r, None)
                 L, H = self.filtered_ranks(logits, mask, flag, all_t, E)
@@ -431,6 +426,86 @@ class TrainerPredictor(object):
             logging.info("MR   : {:.6f}".format(m["MR"]))
             logging.info("MRR  : {:.6f}".format(m["MRR"]))
         return m["MRR"]
+
+    def _device_eval_batches(self, split, eval_set):
+        """The split's DeviceEvalBatches (rows and filter flags built on the
+        device), kept per split and checked against the dataset object."""
+        if not hasattr(self, "_dev_eval"):
+            self._dev_eval = {}
+        cached = self._dev_eval.get(split)
+        if cached is None or cached.eval_set is not eval_set:
+            cached = self._dev_eval[split] = DeviceEvalBatches(eval_set, self.device)
+        return cached
+
+    # ------------------------------------------------------------------ predictions
+    def rule_text(self, rule):
+        """(head, [body...]) in relation names: `head <- b1, b2`."""
+        name = self.model.graph.id2relation
+        head, body = rule
+        return "%s <- %s" % (name.get(head, str(head)), ", ".join(name.get(b, str(b)) for b in body))
+
+    @torch.no_grad()
+    @_native.on_self_device
+    def predict(self, split, k=10, filtered=True, explain=0, output=None):
+        """The model's answers on a split: for every row (h, r, t) the first k
+        tails of (h, r, ?) by score (ties by entity id; rnnl_topk_rows), among
+        the rule-reached candidates and, when `filtered`, without the other
+        known answers of (h, r) — t itself stays in, so its place can be read.
+
+        Rows as in evaluate (the rank's DistributedSampler batches, gathered
+        over the ranks), but without evaluate's RNG draw: a call between two
+        evaluations leaves a seeded run's random sequence alone.  Returns a
+        dict of numpy arrays: h, r, t (n,), index / score (n, k), valid (n,),
+        position (n,) = the 0-based place of t in its row's list or -1, and
+        with explain = m > 0 the CSR explain_off (n m + 1,), explain_rule,
+        explain_count of each row's first m predictions (explain_rows).
+        output: rank 0 writes one TSV line per prediction — head, relation,
+        rank (1-based), tail, score, `*` on the known answer, then up to m
+        `rule:count` pairs in relation names, the rules with most paths first."""
+        eval_set = getattr(self, "%s_set" % split)
+        model = self.model
+        model.eval()
+        dev = self.device
+        if dev.type != "cuda" or not hasattr(model, "predict_topk"):
+            raise RuntimeError("predict runs on the HIP path: it needs a GPU and a Predictor / PredictorPlus model")
+        sampler = torch_data.DistributedSampler(eval_set, self.world_size, self.rank)
+        all_h, all_r, all_t, flag = self._device_eval_batches(split, eval_set).rows(list(iter(sampler)))
+        index, score, valid = model.predict_topk(all_h, all_r, k, flag=flag if filtered else None, keep=all_t)
+        hit = index == all_t.to(torch.int32).unsqueeze(1)
+        position = torch.where(hit.any(1), hit.to(torch.int32).argmax(1), torch.full_like(all_t, -1))
+        out = dict(h=all_h, r=all_r, t=all_t, index=index, score=score, valid=valid, position=position)
+        m = min(int(explain), int(k))
+        if m > 0:
+            off, rule, count = model.explain_rows(all_h, all_r, index[:, :m])
+            out["explain_len"] = (off[1:] - off[:-1]).view(-1, m)  # per slot, so the ranks' CSRs concatenate
+            out["explain_rule"], out["explain_count"] = rule, count
+        if self.world_size > 1:
+            out = comm.cat(out)
+        out = {key: v.cpu().numpy() for key, v in out.items()}
+        if m > 0:
+            lens = out.pop("explain_len").reshape(-1)
+            out["explain_off"] = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        if output is not None and comm.get_rank() == 0:
+            self._write_predictions(os.path.expanduser(output), out, m)
+        return out
+
+    def _write_predictions(self, path, out, m):
+        graph = self.model.graph
+        ent, rel = graph.id2entity, graph.id2relation
+        rules = self.model.rules
+        with open(path, "w") as fo:
+            for i in range(len(out["h"])):
+                h, r, t = int(out["h"][i]), int(out["r"][i]), int(out["t"][i])
+                for j in range(int(out["valid"][i])):
+                    e = int(out["index"][i, j])
+                    cols = [ent[h], rel[r], str(j + 1), ent[e], repr(float(out["score"][i, j])),
+                            "*" if e == t else ""]
+                    if j < m:
+                        a, b = out["explain_off"][i * m + j], out["explain_off"][i * m + j + 1]
+                        pairs = sorted(zip(out["explain_count"][a:b].tolist(), out["explain_rule"][a:b].tolist()),
+                                       key=lambda cr: (-cr[0], cr[1]))[:m]
+                        cols += ["%s:%d" % (self.rule_text(rules[ri]), c) for c, ri in pairs]
+                    fo.write("\t".join(cols) + "\n")
 
     # ------------------------------------------------------------------ checkpoints
     def load(self, checkpoint, load_optimizer=True):
