@@ -34,7 +34,8 @@ constexpr int MAXE_BITS = 19;   // |E| <= 2^MAXE_BITS
 // duplicate (node, entity) entries) and only a window of more than HB_LOAD
 // contributions takes the dense direct-mapped pass.
 constexpr int SORT_WINS = 256;
-constexpr int MAX_SBITS = MAXE_BITS - 10;  // 2^MAXE_BITS / SORT_WINS entities per window at most
+constexpr int MAX_SBITS = MAXE_BITS - 8;  // 2^MAXE_BITS / SORT_WINS entities per window at most
+static_assert((SORT_WINS << MAX_SBITS) == (1 << MAXE_BITS), "SORT_WINS windows of 2^MAX_SBITS entities hold 2^MAXE_BITS");
 static_assert((1 << MAX_SBITS) <= WIN, "a sort window must fit the dense pass's direct map");
 constexpr int HB = WIN;                // phase-B candidate hash slots
 constexpr int HB_LOAD = HB * 3 / 4;    // max contributions per hash pass

@@ -373,9 +373,12 @@ __device__ int window_pass(const KParams &p, SmemT<G> &S, const Ent *w, int lo, 
 // through an LDS bitmap of the pass's entity range, as window_pass's slots
 // are), so a query's candidate records — and the scoring pass's score
 // accesses, one lane per candidate — run along the score row; a range wider
-// than sort_words(G) x 32 entities keeps the hash order (nothing downstream
-// depends on the order for correctness: scores scatter by entity, PNA's mean
-// and the digests are order-independent sums).
+// than sort_words(G) x 32 entities keeps the hash order and leaves duplicate
+// (node, entity) entries unmerged (nothing downstream depends on either for
+// correctness: scores scatter by entity, PNA's mean and the digests are
+// order-independent sums, explain_rows sorts the exported candidates, the
+// autograd COO path sums a bucket's entries in float64;
+// tests/test_gpu_synth_ground.py).
 template <int G>
 __device__ __forceinline__ int hb_slot(SmemT<G> &S, int t, bool insert) {
   uint32_t h = hash32((uint32_t)t) >> (32 - WBITS);

@@ -239,9 +239,13 @@ class _HipGrounding(object):
         reference's stacked rule_count matrix (HIP: rnnl_ground + export).
 
         Returns (row (C,), entity (C,), cand_of_entry (P,), node (P,), count (P,))
-        int64 device tensors: candidates in row-major order (= the reference's
-        nonzero order, predictors.py:239) and, per candidate, its (trie node,
-        path count) entries; node ids index `native_rules(device).node_of_rule`."""
+        int64 device tensors: candidates row by row — within a row ascending
+        by entity (the reference's nonzero order, predictors.py:239) except
+        for the candidates of a grounding pass that spans more entities than
+        it can rank (ground.hip hash_pass: graphs past 49,152 entities), which
+        come in hash order — and, per candidate, its (trie node, path count)
+        entries, where one node may occur more than once; node ids index
+        `native_rules(device).node_of_rule`."""
         device = all_h.device
         nq = all_h.numel()
         totals = np.zeros(2, dtype=np.int64)  # (candidates, bucket entries) with the status read-back
@@ -504,13 +508,16 @@ class _HipGrounding(object):
             C = ent.numel()
             if C == 0:
                 continue
-            cand_key = row * E + ent  # ascending: candidates are row-major by entity
+            # row-major; within a row ascending by entity except where a
+            # grounding pass spans more entities than it can rank (ground.hip
+            # hash_pass: hash order on graphs past 49,152 entities): sorted here
+            cand_key, by_key = torch.sort(row * E + ent)
             want = (torch.arange(rows, device=device).unsqueeze(1) * E + ents)[asked]
             slot = (torch.arange(s0, s0 + rows, device=device).unsqueeze(1) * m
                     + torch.arange(m, device=device).unsqueeze(0))[asked]
             c = torch.searchsorted(cand_key, want).clamp(max=C - 1)
             hit = cand_key[c] == want
-            c, slot = c[hit], slot[hit]
+            c, slot = by_key[c[hit]], slot[hit]
             # the entries of candidate c are ce == c, contiguous
             n_ent = torch.bincount(ce, minlength=C)
             e_off = torch.cumsum(n_ent, 0) - n_ent
@@ -2001,7 +2008,18 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         # (8 ms of a 16.5 ms FB15k-237 training step)
         cnt = count.to(x_f.dtype).unsqueeze(-1)
         node_sum = torch.zeros((nr.n_nodes, H), device=device, dtype=x_f.dtype).index_add(0, nodes, x_f)
-        wsum = torch.zeros((C, H), device=device, dtype=x_f.dtype).index_add(0, ce, cnt * node_sum.index_select(0, node))
+        # a candidate's bucket may hold one node in thousands of entries (the
+        # grounding merges them only in its ranked hash passes) where the
+        # reference multiplies by one count: the entries are summed in float64
+        # — one rounding, as the reference's product — forward and, through
+        # autograd, backward.  In fp32 the 5,000-entry candidates of
+        # tests/test_gpu_synth_ground.py moved a PNA training loss by 3e-4
+        # (std = sqrt(E[x^2] - E[x]^2) cancels by the degree) and rule
+        # gradients by up to 9 %
+        acc = torch.float64
+        cnt64 = count.to(acc).unsqueeze(-1)
+        wsum = torch.zeros((C, H), device=device, dtype=acc).index_add(
+            0, ce, cnt64 * node_sum.to(acc).index_select(0, node)).to(x_f.dtype)
         cand_nan = None
         if nonfinite:
             cand_nan = self._reference_nonfinite(device, all_r, ridx, x_f, row, ce, node, C)[0]
@@ -2017,7 +2035,8 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
                 0, idx_n, x_f, "amin", include_self=True)
             node_max = torch.full((nr.n_nodes, H), float("-inf"), device=device, dtype=x_f.dtype).scatter_reduce(
                 0, idx_n, x_f, "amax", include_self=True)
-            wsq = torch.zeros((C, H), device=device, dtype=x_f.dtype).index_add(0, ce, cnt * node_sq.index_select(0, node))
+            wsq = torch.zeros((C, H), device=device, dtype=acc).index_add(
+                0, ce, cnt64 * node_sq.to(acc).index_select(0, node)).to(x_f.dtype)
             if cand_nan is not None:
                 wsq = torch.where(cand_nan, torch.full_like(wsq, float("nan")), wsq)
             deg = torch.zeros(C, device=device, dtype=x_f.dtype).index_add(0, ce, cnt.squeeze(-1) * node_n.index_select(0, node)) + 1

@@ -13,6 +13,13 @@ loop, each output is compared
   tests/test_gpu_forward.py applies to the DIRECT mode;
 * bitwise with the accumulating, atomic and two-piece launches;
 * (split form, 45 rows) bitwise with the first rows of the one-pass launch.
+
+The opt-in MFMA kernel (mode = ROTATE_MFMA, the expanded bf16x3 form) runs the
+same shapes against the float64 evaluation alone: within TOL on every entry
+but the candidates at (nearly) zero distance, the expanded form's cancellation
+case, which are held to the bound that tests/test_gpu_forward.py computes for
+such rows (run_mfma_case).  The recorded parent outputs are the DIRECT
+kernels' and do not apply to it.
 """
 import os
 import sys
@@ -115,3 +122,83 @@ def test_chunk_boundary(D, dev, tmp_path):
     small = run_case(tmp_path / "split", dev, D, gen.BIG_E, gen.SPLIT_ROWS)
     # (4) the split form == the one-pass kernel on the same rows
     assert torch.equal(small, big[:gen.SPLIT_ROWS]), float((small - big[:gen.SPLIT_ROWS]).abs().max())
+
+
+def mfma_reference(eemb, remb2, gamma, h, r, dev):
+    """(float64 scores, per-entry allowance) for the expanded MFMA form.
+
+    DESIGN.md "RotatE numerics": the form reaches each term's squared distance
+    s_d = |hr_d - t_d|^2 through |hr_d|^2 + |t_d|^2 - 2 hr_d . t_d, with an
+    absolute error of up to delta_d = c 2^-24 (|hr_d|^2 + |t_d|^2), c = 8.
+    The term sqrt(s_d) then moves by at most
+    max(sqrt(s_d + delta_d) - sqrt(s_d), sqrt(s_d) - sqrt(max(s_d - delta_d, 0))):
+    sqrt(delta_d) where h o r = t — summed over d, the bound that
+    tests/test_gpu_forward.py's test_rotate_scores_vs_float64 applies to its
+    near-match rows — and ~delta_d / (2 sqrt(s_d)), far below TOL, on an
+    ordinary entry.  Nothing here comes from the kernel under test."""
+    D = eemb.shape[1] // 2
+    div = np.float32((gamma + 2.0) / D / np.pi)
+    ph = (remb2[r] / div).astype(np.float64)
+    e = eemb.astype(np.float64)
+    hh = e[h]
+    re = torch.from_numpy(hh[:, :D] * np.cos(ph) - hh[:, D:] * np.sin(ph)).to(dev)
+    im = torch.from_numpy(hh[:, :D] * np.sin(ph) + hh[:, D:] * np.cos(ph)).to(dev)
+    et = torch.from_numpy(e).to(dev)
+    tn = et[:, :D] ** 2 + et[:, D:] ** 2
+    want = torch.empty((len(h), e.shape[0]), dtype=torch.float64, device=dev)
+    allow = torch.empty_like(want)
+    for i in range(0, len(h), 512):
+        b = slice(i, i + 512)
+        sq = (re[b, None] - et[None, :, :D]) ** 2 + (im[b, None] - et[None, :, D:]) ** 2
+        delta = 8 * 2.0 ** -24 * ((re[b] ** 2 + im[b] ** 2)[:, None] + tn[None])
+        root = torch.sqrt(sq)
+        want[b] = gamma - root.sum(2)
+        allow[b] = torch.maximum(torch.sqrt(sq + delta) - root, root - torch.sqrt((sq - delta).clamp(min=0))).sum(2)
+    return want, allow
+
+
+def run_mfma_case(tmp_path, dev, D, E, n):
+    """Every entry within TOL, or within the expanded form's documented
+    allowance where that is larger: the candidates at (nearly) zero distance
+    — row 0's head, make_inputs' planted near match of row 1, and the head of
+    every other row that queries the zero-phase relation 0 or its inverse —
+    and the few entries with one dim nearly equal by chance."""
+    from rnnlogic_amd import _native
+    from rnnlogic_amd.embedding import RotatE
+    eemb, remb, h, r = gen.make_inputs(D, E)
+    h, r = h[:n], r[:n]
+    gen.write_tables(str(tmp_path), eemb, remb)
+    rot = RotatE(str(tmp_path)).to(dev)
+    rot.mode = _native.ROTATE_MFMA
+    hh, rr = torch.from_numpy(h).to(dev), torch.from_numpy(r).to(dev)
+    k = gen.key(D, E, n)
+    with torch.no_grad():
+        got = rot(hh, rr)
+        want, allow = mfma_reference(eemb, np.concatenate([remb, -remb]), gen.GAMMA, h, r, dev)
+        err = (got.double() - want).abs()
+        loose = allow > TOL
+        zero = torch.zeros_like(err)
+        plain = float(torch.where(loose, zero, err).max())
+        worst = float((err / allow.clamp(min=TOL)).max())
+        print("%s MFMA: max |score - f64| %.3g where the allowance is <= TOL; %d of %d entries allow more "
+              "(max err there %.3g, allowance up to %.3g; largest err / allowance %.3g)"
+              % (k, plain, int(loose.sum()), err.numel(), float(torch.where(loose, err, zero).max()),
+                 float(allow.max()), worst))
+        assert float(allow[0, h[0]]) > TOL, k  # row 0: zero phases, the head is a candidate
+        assert int(loose.sum()) <= 2 * n + err.numel() // 50, k  # the planted ones and a few by chance
+        assert plain <= TOL, "%s: max |score - f64| = %g" % (k, plain)
+        assert bool((err <= allow.clamp(min=TOL)).all()), (k, worst)
+        acc = rot.score_into(hh, rr, torch.zeros_like(got), accumulate=True)
+        assert torch.equal(acc, got), (k, "accumulate=True")
+    return got
+
+
+@pytest.mark.parametrize("D,E,n", gen.small_cases())
+def test_mfma_one_chunk(D, E, n, dev, tmp_path):
+    run_mfma_case(tmp_path, dev, D, E, n)
+
+
+@pytest.mark.parametrize("D", gen.BIG_D)
+def test_mfma_chunk_boundary(D, dev, tmp_path):
+    run_mfma_case(tmp_path / "big", dev, D, gen.BIG_E, gen.BIG_ROWS)
+    run_mfma_case(tmp_path / "split", dev, D, gen.BIG_E, gen.SPLIT_ROWS)
