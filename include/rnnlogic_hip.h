@@ -596,6 +596,58 @@ int rnnl_miner_destroy(rnnl_miner m);
 int rnnl_rule_search(rnnl_miner m, int32_t max_length, uint64_t *table, int64_t table_cap, uint64_t *rules_out,
                      int64_t out_cap, uint64_t *counters, void *stream);
 
+/* ------------------------------------------ rule weights and H scores --
+ * What the reference miner does after its search (miner/main.cpp:40-48): one
+ * weight per rule learned by online Adam over the train triples
+ * (ReasoningPredictor::learn, rnnlogic.cpp:728-845) and an H score per rule
+ * (H_score, :847-940), single-threaded semantics: a pure function of the
+ * triple order, bitwise repeatable.  All values are fp64.
+ *
+ *   rnnl_miner_set_rules (host arrays, synchronous): relation r's rules are
+ *     [rule_off[r], rule_off[r + 1]) (rule_off[0] = 0, R + 1 entries), rule i
+ *     has body rule_body[3 i .. 3 i + rule_len[i]) (length 0..3; an empty body
+ *     reaches nothing), prior[i] (NULL: 0).  Clears weights, Adam state and H.
+ *
+ * The triples are walked in chunks that the caller cuts (to its memory
+ * budget): order (device, int32 indices into the triples given to
+ * rnnl_miner_create) positions [begin, begin + count).  pair_base (device,
+ * count + 1, exclusive sum of the number of rules of each position's relation)
+ * numbers the chunk's (triple, rule) pairs; n_pairs = pair_base[count].
+ *   rnnl_miner_ground_count: pair_off (device, n_pairs + 1) receives the
+ *     exclusive sum of the number of destinations per pair; counters (device,
+ *     4 x uint64, zeroed here): [0] = number of entries, [1] != 0: a path
+ *     count does not fit u32 (RNNL_ERR_RANGE for the caller to raise),
+ *     [2] != 0: an order index out of range, [3] != 0: internal mismatch.
+ *   rnnl_miner_ground_fill: ent_dst / ent_cnt (device, ent_cap >= counters[0])
+ *     receive per pair its (destination ascending, path count) entries, the
+ *     triple's own edge (h, r, t) and every copy of it skipped on every hop
+ *     (KnowledgeGraph::rule_destination, :412-442).  counters is not zeroed.
+ *   rnnl_miner_learn: the chunk's learn steps, one workgroup per relation in
+ *     order of position; weights and Adam state stay in the handle between
+ *     chunks.  fast != 0: one update with grad * count per entry.
+ *   rnnl_miner_h_score: the chunk's H_score steps (top_k == 0: softmax over
+ *     the relation's rules; top_k > 0: the top_k largest val, ties by position
+ *     in the list, get 1 / top_k); shares are divided by the number of triples
+ *     of the handle and added to H.
+ *   rnnl_miner_read: copies weights / H (device, n_rules doubles, either may
+ *     be NULL) out of the handle.
+ * All but set_rules are asynchronous on `stream`. */
+int rnnl_miner_set_rules(rnnl_miner m, const int32_t *rule_off, const int32_t *rule_len, const int32_t *rule_body,
+                         const double *prior);
+int rnnl_miner_ground_count(rnnl_miner m, const int32_t *order, int64_t begin, int64_t count,
+                            const int64_t *pair_base, int64_t n_pairs, int64_t *pair_off, uint64_t *counters,
+                            void *stream);
+int rnnl_miner_ground_fill(rnnl_miner m, const int32_t *order, int64_t begin, int64_t count,
+                           const int64_t *pair_base, int64_t n_pairs, const int64_t *pair_off, int32_t *ent_dst,
+                           uint32_t *ent_cnt, int64_t ent_cap, uint64_t *counters, void *stream);
+int rnnl_miner_learn(rnnl_miner m, const int32_t *order, int64_t begin, int64_t count, const int64_t *pair_base,
+                     int64_t n_pairs, const int64_t *pair_off, const int32_t *ent_dst, const uint32_t *ent_cnt,
+                     double lr, double wd, double temp, int32_t fast, void *stream);
+int rnnl_miner_h_score(rnnl_miner m, const int32_t *order, int64_t begin, int64_t count, const int64_t *pair_base,
+                       int64_t n_pairs, const int64_t *pair_off, const int32_t *ent_dst, const uint32_t *ent_cnt,
+                       int32_t top_k, double h_temperature, double prior_weight, void *stream);
+int rnnl_miner_read(rnnl_miner m, double *weights, double *H, void *stream);
+
 /* ------------------------------------------------------- training loss --
  * TrainerPredictor.train's loss (reference src/trainer.py:84-90) for a model
  * whose mask is all True (bias / RotatE features): with

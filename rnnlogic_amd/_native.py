@@ -103,6 +103,14 @@ SIGNATURES = [
     ("rnnl_miner_create", ctypes.c_int, [_P, _I64, _I32, _I32, _P]),
     ("rnnl_miner_destroy", ctypes.c_int, [_P]),
     ("rnnl_rule_search", ctypes.c_int, [_P, _I32, _P, _I64, _P, _I64, _P, _P]),
+    ("rnnl_miner_set_rules", ctypes.c_int, [_P, _P, _P, _P, _P]),
+    ("rnnl_miner_ground_count", ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, _P, _P]),
+    ("rnnl_miner_ground_fill", ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P]),
+    ("rnnl_miner_learn", ctypes.c_int,
+     [_P, _P, _I64, _I64, _P, _I64, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I32, _P]),
+    ("rnnl_miner_h_score", ctypes.c_int,
+     [_P, _P, _I64, _I64, _P, _I64, _P, _P, _P, _I32, ctypes.c_double, ctypes.c_double, _P]),
+    ("rnnl_miner_read", ctypes.c_int, [_P, _P, _P, _P]),
     ("rnnl_rotate_score", ctypes.c_int,
      [_P, _P, _P, _I32, _F32, _P, _P, _I32, _I32, _P, _I32, _I32, _P, ctypes.c_size_t, _P]),
     ("rnnl_rotate_score_pieces", ctypes.c_int,

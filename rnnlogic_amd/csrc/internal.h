@@ -40,6 +40,19 @@ struct MinerDev {
   const int32_t *th = nullptr, *tr = nullptr, *tt = nullptr;                 // n
 };
 
+// What the miner's learn / H_score stage adds to the handle (mine_learn.hip):
+// the out-edges once more, sorted by (source, relation, target) under the same
+// out_off, the current rule lists and one Adam parameter + H per rule.
+struct MinerLearnDev {
+  const int32_t *so_rel = nullptr, *so_dst = nullptr;  // n, n
+  int32_t n_rules = 0;
+  const int32_t *rule_off = nullptr;   // R + 1: relation r's rules are [rule_off[r], rule_off[r + 1])
+  const int32_t *rule_len = nullptr;   // n_rules, 0..3
+  const int32_t *rule_body = nullptr;  // n_rules x 3
+  const double *prior = nullptr;       // n_rules
+  double *wt = nullptr, *am = nullptr, *av = nullptr, *at = nullptr, *H = nullptr, *val = nullptr;  // n_rules
+};
+
 // Rule bodies as one prefix trie per head relation.  Node ids are global;
 // the nodes of one head are contiguous, numbered breadth-first, so the
 // children of a node are contiguous too.  Node 0 of a head is its root
@@ -91,6 +104,15 @@ int rotate_score_rows(const float *eemb, const void *etab, const float *rtab, in
                       float first_share, const int32_t *row_of, void *stream);
 
 }  // namespace rnnl
+
+struct rnnl_miner_s {
+  rnnl::MinerDev d;
+  rnnl::MinerLearnDev l;
+  std::vector<void *> bufs;       // the graph (rnnl_miner_create)
+  std::vector<void *> rule_bufs;  // rule lists, parameters, scratch (rnnl_miner_set_rules)
+  unsigned char *ground_scratch = nullptr, *chain_scratch = nullptr;
+  int32_t ground_blocks = 0;
+};
 
 struct rnnl_graph_s {
   rnnl::GraphDev d;

@@ -27,11 +27,6 @@
 
 #include "internal.h"
 
-struct rnnl_miner_s {
-  rnnl::MinerDev d;
-  std::vector<void *> bufs;
-};
-
 namespace rnnl {
 
 constexpr int MB = 256;             // threads per workgroup
@@ -266,6 +261,20 @@ int rnnl_miner_create(const int32_t *hrt, int64_t n, int32_t E, int32_t R, rnnl_
     tr[i] = hrt[3 * i + 1];
     tt[i] = hrt[3 * i + 2];
   }
+  // the out-edges once more, sorted by (relation, target) within a source (mine_learn.hip)
+  std::vector<int32_t> so_rel(n), so_dst(n);
+  {
+    std::vector<std::pair<int32_t, int32_t>> tmp;
+    for (int32_t e = 0; e < E; ++e) {
+      tmp.clear();
+      for (int32_t k = out_off[e]; k < out_off[e + 1]; ++k) tmp.emplace_back(out_rel[k], out_dst[k]);
+      std::sort(tmp.begin(), tmp.end());
+      for (size_t k = 0; k < tmp.size(); ++k) {
+        so_rel[out_off[e] + k] = tmp[k].first;
+        so_dst[out_off[e] + k] = tmp[k].second;
+      }
+    }
+  }
   rnnl_miner_s *mm = new rnnl_miner_s;
   auto up = [&](const std::vector<int32_t> &v, const int32_t *&dst) -> int {
     void *p = nullptr;
@@ -283,7 +292,8 @@ int rnnl_miner_create(const int32_t *hrt, int64_t n, int32_t E, int32_t R, rnnl_
   for (auto pr : {std::make_pair(&out_off, &mm->d.out_off), std::make_pair(&out_dst, &mm->d.out_dst),
                   std::make_pair(&out_rel, &mm->d.out_rel), std::make_pair(&in_off, &mm->d.in_off),
                   std::make_pair(&in_src, &mm->d.in_src), std::make_pair(&in_rel, &mm->d.in_rel),
-                  std::make_pair(&th, &mm->d.th), std::make_pair(&tr, &mm->d.tr), std::make_pair(&tt, &mm->d.tt)})
+                  std::make_pair(&th, &mm->d.th), std::make_pair(&tr, &mm->d.tr), std::make_pair(&tt, &mm->d.tt),
+                  std::make_pair(&so_rel, &mm->l.so_rel), std::make_pair(&so_dst, &mm->l.so_dst)})
     if (rc == RNNL_OK) rc = up(*pr.first, *pr.second);
   if (rc != RNNL_OK) {
     for (void *p : mm->bufs) (void)hipFree(p);
@@ -298,6 +308,7 @@ int rnnl_miner_create(const int32_t *hrt, int64_t n, int32_t E, int32_t R, rnnl_
 int rnnl_miner_destroy(rnnl_miner m) {
   if (!m) return RNNL_OK;
   for (void *p : m->bufs) (void)hipFree(p);
+  for (void *p : m->rule_bufs) (void)hipFree(p);
   delete m;
   return RNNL_OK;
 }

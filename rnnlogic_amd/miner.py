@@ -1,15 +1,35 @@
-"""RuleMiner, API-compatible with the reference's rule-search stage
-(miner/rnnlogic.cpp RuleMiner: search :505-589, get_logic_rules, save
-:591-610), with the search on the GPU (rnnl_rule_search, csrc/mine.hip).
+"""RuleMiner: the reference miner (miner/main.cpp:27-49) on the GPU — the rule
+search (RuleMiner::search, rnnlogic.cpp:505-589; rnnl_rule_search,
+csrc/mine.hip), then one weight per rule learned by online Adam
+(ReasoningPredictor::learn), the H score per rule (H_score), the pool's
+running mean (RuleGenerator::update) and the rule file (out_rules)
+(rnnl_miner_learn / rnnl_miner_h_score, csrc/mine_learn.hip).
 
     miner = RuleMiner(graph)            # graph: rnnlogic_amd.data.KnowledgeGraph
     rules = miner.search(max_length=3)  # [(head, body tuple)] in the reference's order
-    miner.save("mined_rules.txt")       # "type head body... H wt prior", as RuleMiner::save
+    miner.save("pool.txt")              # "type head body... H wt prior", as RuleMiner::save
+
+    miner.mine(max_length=3, iterations=1, top_n=0, top_k=0, lr=0.01, wd=0.0005, temp=100)
+    miner.out_rules("mined_rules.txt", top_n_out=0)    # "head body... H", H descending per relation
+
+    miner.set_logic_rules(rel2rules)    # or step by step, as ReasoningPredictor
+    miner.learn(lr, wd, temp); miner.h_score(top_k); miner.weights(); miner.H()
+
+    python -m rnnlogic_amd.miner -data-path D -output-file F -max-length 3 ...   # main.cpp's flags
 
 The pool equals the reference's for the same train graph: every relation
 path of length <= max_length from h to t of a train triple (h, r, t), the
 triple's own edge removed, as the rule r <- path; r <- r dropped; per head in
 std::set<Rule> order (length, then body).  max_length <= 3.
+
+learn / h_score compute what the reference computes with one thread: a pure
+function of the triple order (its multi-threaded run races on the weights and
+is not reproducible), in fp64, bitwise repeatable and independent of how the
+triples are cut into chunks.  The orders and rule subsets are drawn from
+seeded numpy generators, or given (`orders`, `selections`) to replay a
+reference run.  Where the reference leaves ties to std::sort they are defined
+here: top-k by val descending then position in the rule list, out_rules by H
+descending then pool order.
 """
 import ctypes
 
@@ -31,6 +51,16 @@ class RuleMiner(object):
                          ctypes.byref(self._handle))
         self.rules = []
         self.table_bits = 22
+        self._hrt = hrt
+        self._searched = None
+        self._counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self._rng = np.random.default_rng(0)  # triple orders of learn() calls without one
+        self._order = None
+        self._rule_off = np.zeros(graph.relation_size + 1, dtype=np.int32)
+        self._grounded = None
+        self.pool, self.pool_H = None, None
+        self.chunk_triples = None     # triples per grounding chunk; None: as many as budget_bytes allows
+        self.budget_bytes = 1 << 30   # device memory for one chunk's (triple, rule, destination, count) entries
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -70,7 +100,14 @@ class RuleMiner(object):
 
     def search(self, max_length):
         """RuleMiner::search over all train triples (portion 1)."""
-        self.rules = self.decode(self.search_keys(max_length))
+        keys = np.sort(self.search_keys(max_length))
+        self.rules = self.decode(keys)
+        m = np.uint64(0x7FFF)
+        self._pool_arrays = ((keys >> np.uint64(47)).astype(np.int64),  # head, length, body of self.rules
+                             ((keys >> np.uint64(45)) & np.uint64(3)).astype(np.int32),
+                             np.stack([(keys >> np.uint64(30)) & m, (keys >> np.uint64(15)) & m, keys & m],
+                                      1).astype(np.int32))
+        self._searched = max_length
         return self.rules
 
     def get_logic_rules(self):
@@ -80,6 +117,206 @@ class RuleMiner(object):
             rel2rules[hd].append((hd, body))
         return rel2rules
 
+    # ------------------------------------------------- weights and H scores
+    def set_logic_rules(self, rel2rules, priors=None):
+        """ReasoningPredictor::set_logic_rules: rel2rules[r] = [(head, body)]
+        are relation r's rules, in list order; weights, Adam state and H are
+        cleared.  priors[r][k] (default 0) enters h_score with prior_weight."""
+        R = self.graph.relation_size
+        if len(rel2rules) != R:
+            raise ValueError("set_logic_rules: one rule list per relation expected")
+        off, ln, body, pr = [0], [], [], []
+        for r, rules in enumerate(rel2rules):
+            for k, (hd, b) in enumerate(rules):
+                if int(hd) != r:
+                    raise ValueError("set_logic_rules: rule with head %d in the list of relation %d" % (hd, r))
+                if len(b) > 3:
+                    raise ValueError("set_logic_rules: rule bodies have at most 3 relations")
+                ln.append(len(b))
+                body.append([int(x) for x in b] + [0] * (3 - len(b)))
+                pr.append(float(priors[r][k]) if priors is not None else 0.0)
+            off.append(len(ln))
+        self._set_rule_arrays(off, ln, np.asarray(body, dtype=np.int32).reshape(-1, 3), pr)
+
+    def _set_rule_arrays(self, off, ln, body, prior):
+        self._rule_off = np.ascontiguousarray(off, dtype=np.int32)
+        ln = np.ascontiguousarray(ln, dtype=np.int32)
+        body = np.ascontiguousarray(body, dtype=np.int32)
+        pr = np.ascontiguousarray(prior, dtype=np.float64)
+        with torch.cuda.device(self.device):
+            _native.call("rnnl_miner_set_rules", self._handle, self._rule_off.ctypes.data, ln.ctypes.data,
+                         body.ctypes.data, pr.ctypes.data)
+        self._grounded = None
+
+    def _use_order(self, order, portion):
+        n = len(self._hrt)
+        if order is None:
+            order = self._order if self._order is not None else self._rng.permutation(n)
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        if order.shape != (n,) or not np.array_equal(np.sort(order), np.arange(n, dtype=np.int32)):
+            raise ValueError("order must be a permutation of range(%d), the train triples" % n)
+        self._order = order
+        return order, int(n * portion)
+
+    def _ground(self, order_dev, begin, count, pair_base, stream):
+        """The (triple, rule, destination, count) entries of one chunk, or
+        None if they would exceed the byte budget and the chunk can be cut."""
+        n_pairs = int(pair_base[-1])
+        pb = torch.from_numpy(pair_base).to(self.device)
+        pair_off = torch.empty(n_pairs + 1, dtype=torch.int64, device=self.device)
+        _native.call("rnnl_miner_ground_count", self._handle, order_dev.data_ptr(), begin, count, pb.data_ptr(),
+                     n_pairs, pair_off.data_ptr(), self._counters.data_ptr(), stream)
+        total = self._check_counters()
+        if total * 8 > self.budget_bytes and count > 1 and self.chunk_triples is None:
+            return None
+        dst = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)  # u32 path counts
+        _native.call("rnnl_miner_ground_fill", self._handle, order_dev.data_ptr(), begin, count, pb.data_ptr(),
+                     n_pairs, pair_off.data_ptr(), dst.data_ptr(), cnt.data_ptr(), total,
+                     self._counters.data_ptr(), stream)
+        self._check_counters()  # the chain kernels index by these entries: read them only if they are whole
+        return (begin, count, pb, n_pairs, pair_off, dst, cnt)
+
+    def _check_counters(self):
+        c = self._counters.cpu().tolist()
+        if c[1]:
+            raise _native.NativeError(_native.RNNL_ERR_RANGE, "rule miner: a path count does not fit 32 bits")
+        if c[2] or c[3]:
+            raise _native.NativeError(_native.RNNL_ERR_INTERNAL, "rule miner: grounding failed (flags %r)" % (c[1:],))
+        return int(c[0])
+
+    def _chunks(self, order, n_used, stream):
+        """Ground positions [0, n_used) of `order` chunk by chunk: whole chunks
+        of chunk_triples if that is set, else as many triples as the byte
+        budget allows (16 bytes per pair, 8 per entry)."""
+        key = (hash(order.tobytes()), n_used)
+        if self._grounded is not None and self._grounded[0] == key and np.array_equal(self._grounded[2], order):
+            yield self._grounded[1]
+            return
+        order_dev = torch.from_numpy(order).to(self.device)
+        nr_of = (self._rule_off[1:] - self._rule_off[:-1]).astype(np.int64)[self._hrt[order[:n_used], 1]]
+        begin, first = 0, True
+        step = self.chunk_triples
+        while begin < n_used:
+            if step is None:
+                cum = np.cumsum(nr_of[begin:])
+                count = max(1, int(np.searchsorted(cum, self.budget_bytes // 16, side="right")))
+            else:
+                count = min(step, n_used - begin)
+            while True:
+                pair_base = np.zeros(count + 1, dtype=np.int64)
+                np.cumsum(nr_of[begin:begin + count], out=pair_base[1:])
+                chunk = self._ground(order_dev, begin, count, pair_base, stream)
+                if chunk is not None:
+                    break
+                count = max(1, count // 2)
+            chunk = chunk + (order_dev,)
+            if first and count == n_used:  # the whole run in one chunk: h_score reuses learn's entries
+                self._grounded = (key, chunk, order.copy())  # (kept until the rules are set again)
+            first = False
+            yield chunk
+            begin += count
+
+    @torch.no_grad()
+    def learn(self, lr, wd, temp, fast=False, portion=1.0, order=None):
+        """ReasoningPredictor::learn with one thread: online Adam over the
+        first int(n * portion) triples of `order` (a permutation of the train
+        triples; drawn from the miner's seeded generator if absent)."""
+        order, n_used = self._use_order(order if order is not None else self._rng.permutation(len(self._hrt)),
+                                        portion)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            for begin, count, pb, n_pairs, pair_off, dst, cnt, odev in self._chunks(order, n_used, stream):
+                _native.call("rnnl_miner_learn", self._handle, odev.data_ptr(), begin, count, pb.data_ptr(), n_pairs,
+                             pair_off.data_ptr(), dst.data_ptr(), cnt.data_ptr(), float(lr), float(wd), float(temp),
+                             int(bool(fast)), stream)
+
+    @torch.no_grad()
+    def h_score(self, top_k, H_temperature=1.0, prior_weight=0.0, portion=1.0, order=None):
+        """ReasoningPredictor::H_score with one thread, over the order of the
+        last learn() unless one is given (H_score does not shuffle)."""
+        order, n_used = self._use_order(order, portion)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            for begin, count, pb, n_pairs, pair_off, dst, cnt, odev in self._chunks(order, n_used, stream):
+                _native.call("rnnl_miner_h_score", self._handle, odev.data_ptr(), begin, count, pb.data_ptr(),
+                             n_pairs, pair_off.data_ptr(), dst.data_ptr(), cnt.data_ptr(), int(top_k),
+                             float(H_temperature), float(prior_weight), stream)
+
+    def _read(self, which):
+        n = int(self._rule_off[-1])
+        out = torch.empty(n, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.call("rnnl_miner_read", self._handle, out.data_ptr() if which == 0 else None,
+                         out.data_ptr() if which == 1 else None, torch.cuda.current_stream(self.device).cuda_stream)
+        flat = out.cpu().numpy()
+        return [flat[a:b] for a, b in zip(self._rule_off[:-1], self._rule_off[1:])]
+
+    def weights(self):
+        """Per relation, the learned weight of each rule of its list (float64)."""
+        return self._read(0)
+
+    def H(self):
+        """Per relation, the H score of each rule of its list (float64)."""
+        return self._read(1)
+
+    def mine(self, max_length, iterations, top_n, top_k, lr, wd, temp, top_n_out=0, seed=0, orders=None,
+             selections=None, portion=1.0):
+        """The reference miner's main loop (miner/main.cpp:27-49): search, then
+        per iteration a rule subset per relation (top_n, 0 = all), learn,
+        H_score and the pool's running mean of H.  orders[it] (a permutation
+        of the train triples) and selections[it][r] (pool indices) replace the
+        seeded draws, so a reference run can be replayed.  Returns the rules
+        out_rules would write: [(head, body, H)]."""
+        if not self.rules or self._searched != max_length:
+            self.search(max_length)
+        pool = self.get_logic_rules()
+        R = self.graph.relation_size
+        self.pool = pool
+        self.pool_H = [np.zeros(len(p), dtype=np.float64) for p in pool]
+        cn = [np.zeros(len(p), dtype=np.float64) for p in pool]
+        p_head, p_len, p_body = self._pool_arrays  # the pool in search order: per head, then by key
+        pool_off = np.searchsorted(p_head, np.arange(R + 1))
+        rng = np.random.default_rng(seed)
+        for it in range(iterations):
+            if selections is not None:
+                sel = [np.asarray(selections[it][r], dtype=np.int64) for r in range(R)]
+            else:
+                sel = [rng.permutation(len(pool[r]))[:top_n if top_n else None] for r in range(R)]
+            order = np.ascontiguousarray(orders[it] if orders is not None else rng.permutation(len(self._hrt)),
+                                         dtype=np.int32)
+            take = np.concatenate([pool_off[r] + sel[r] for r in range(R)]) if R else np.zeros(0, np.int64)
+            off = np.concatenate([[0], np.cumsum([len(x) for x in sel])])
+            self._set_rule_arrays(off, p_len[take], p_body[take], np.zeros(len(take)))  # = set_logic_rules(subset)
+            self.learn(lr, wd, temp, False, portion, order)
+            self.h_score(top_k, 1.0, 0.0, portion, self._order)
+            for r, H in enumerate(self.H()):  # RuleGenerator::update
+                self.pool_H[r][sel[r]] = (self.pool_H[r][sel[r]] * cn[r][sel[r]] + H) / (cn[r][sel[r]] + 1)
+                cn[r][sel[r]] += 1
+        self._grounded = None
+        return self.best_rules(top_n_out)
+
+    def best_rules(self, top_n_out=0):
+        """Per relation the pool's rules by H descending, then pool order; the
+        first top_n_out (0 = all): [(head, body, H)]."""
+        if self.pool is None:
+            raise RuntimeError("RuleMiner.best_rules / out_rules: call mine() first")
+        out = []
+        for r, rules in enumerate(self.pool):
+            idx = np.argsort(-self.pool_H[r], kind="stable")
+            for k in idx[:top_n_out if top_n_out else None]:
+                out.append((rules[k][0], rules[k][1], float(self.pool_H[r][k])))
+        return out
+
+    def out_rules(self, file_name, top_n_out=0):
+        """RuleGenerator::out_rules (rnnlogic.cpp:1904-1935): 'head body... H'
+        with H as %.16f — the mined_rules.txt of the reference pipeline."""
+        rules = self.best_rules(top_n_out)
+        with open(file_name, "w") as fo:
+            for hd, body, H in rules:
+                fo.write("%d%s %.16f\n" % (hd, "".join(" %d" % x for x in body), H))
+        return len(rules)
+
     def save(self, file_name):
         """RuleMiner::save (rnnlogic.cpp:591-610): 'type head body... H wt prior'
         (H, wt, prior are 0 after a search)."""
@@ -87,3 +324,33 @@ class RuleMiner(object):
             for hd, body in self.rules:
                 fo.write("%d %d%s %f %f %f\n" % (len(body), hd, "".join(" %d" % x for x in body), 0.0, 0.0, 0.0))
         return len(self.rules)
+
+
+def main(argv=None):
+    """python -m rnnlogic_amd.miner: the reference miner's command line
+    (miner/main.cpp) — same flags, same defaults; -threads is accepted and
+    ignored (the GPU run is the single-threaded semantics)."""
+    import argparse
+
+    from .data import KnowledgeGraph
+    ap = argparse.ArgumentParser(prog="python -m rnnlogic_amd.miner", allow_abbrev=False)
+    ap.add_argument("-data-path", dest="data_path", required=True)
+    ap.add_argument("-output-file", dest="output_file", required=True)
+    ap.add_argument("-max-length", dest="max_length", type=int, default=2)
+    ap.add_argument("-threads", dest="threads", type=int, default=1)
+    ap.add_argument("-iterations", dest="iterations", type=int, default=10)
+    ap.add_argument("-lr", dest="lr", type=float, default=0.01)
+    ap.add_argument("-wd", dest="wd", type=float, default=0.0)
+    ap.add_argument("-temp", dest="temp", type=float, default=100.0)
+    ap.add_argument("-top-k", dest="top_k", type=int, default=10)
+    ap.add_argument("-top-n", dest="top_n", type=int, default=100)
+    ap.add_argument("-top-n-out", dest="top_n_out", type=int, default=100)
+    ap.add_argument("-seed", dest="seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    miner = RuleMiner(KnowledgeGraph(a.data_path))
+    miner.mine(a.max_length, a.iterations, a.top_n, a.top_k, a.lr, a.wd, a.temp, a.top_n_out, seed=a.seed)
+    print("#Rules written: %d" % miner.out_rules(a.output_file, a.top_n_out))
+
+
+if __name__ == "__main__":
+    main()

@@ -42,7 +42,10 @@ def _read_rules(input):
     elif isinstance(input, str):
         with open(input, "r") as fi:
             for line in fi:
-                rule = [int(_) for _ in line.strip().split()]
+                tok = line.strip().split()
+                if tok and "." in tok[-1]:  # "head body... H", as the miner's out_rules writes it
+                    tok = tok[:-1]
+                rule = [int(_) for _ in tok]
                 rules.append((rule[0], rule[1:]))
     else:
         raise ValueError
