@@ -759,6 +759,70 @@ int rnnl_ground_wide(rnnl_graph g, rnnl_rules r, const int64_t *all_h, const int
                      uint64_t *out_count, int64_t cap, uint64_t *cursor, void *stream);
 int rnnl_forward_error_bits(void *workspace, void *stream, uint32_t *bits);
 
+/* ------------------------------------------- RotatE embedding training --
+ * The sampled-negative training step of RotatE tables (the model that wrote
+ * the shipped RotatE_<dim> directories): eemb (n_entities x 2 dim, [re | im]),
+ * remb (n_relations x dim), phase = remb / div with the fp32 divisor
+ * div = (gamma + 2) / dim / pi of rnnl_rotate_relation_table.
+ *
+ * A row is a positive (h, r, t) of positives (n_rows x 3, int64) and the
+ * call's mode.  RNNL_KGE_TAIL: anchor h, answer t, query q = h o r;
+ * RNNL_KGE_HEAD: anchor t, answer h, q = t o conj(r).  A candidate entity x
+ * scores s = gamma - sum_d |q_d - x_d| (complex modulus; the gradient is zero
+ * where the modulus is zero, torch.norm's convention).
+ *
+ * rnnl_kge_sample_negatives: neg (n_rows x n_neg, int32) receives, per slot,
+ * an entity that is uniform over those not listed as a true answer of the
+ * row.  The true answers are a CSR map in the layout of rnnl_multi_hot (keys
+ * ascending, offs n_keys + 1, vals int32) whose value lists are ascending and
+ * without repeats; the row's key is r * n_entities + h (tail mode: the list
+ * holds the tails of (h, r)) or r * n_entities + t (head mode: the heads of
+ * (r, t)); a key that is not in the map has no true answer.
+ * The generator is counter-based, all arithmetic modulo 2^64:
+ *   mix(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;
+ *            z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *   G  = 0x9E3779B97F4A7C15
+ *   k0 = mix(seed + G * (step + 1))
+ *   k1 = mix(k0 ^ (row << 32 | slot))
+ *   draw(attempt) = mix(k1 + G * (attempt + 1)) >> 32          attempt = 0, 1, ...
+ *   entity(attempt) = (draw(attempt) * n_entities) >> 32
+ * The slot takes the first entity(attempt) that is not in the row's list
+ * (binary search); after 64 rejected attempts the 64th draw stands and
+ * *capped (one int32, zeroed by the call) counts the slot.  neg is a function
+ * of the arguments alone, not of the launch geometry.
+ *
+ * rnnl_kge_rotate_step: with weights w (n_rows, NULL: all 1), W = sum w,
+ * p_ij = softmax_j(alpha s_ij) taken as a constant (row maximum subtracted;
+ * alpha = 0: the plain mean), pos_i = log sigmoid(s+_i) and
+ * neg_i = sum_j p_ij log sigmoid(-s_ij):
+ *   losses[0] = -sum w_i pos_i / W, losses[1] = -sum w_i neg_i / W,
+ *   losses[2] = (losses[0] + losses[1]) / 2         (3 floats, device)
+ *   pos_score (n_rows) = s+, neg_score (n_rows x n_neg) = s,
+ *   d_eemb (n_entities x 2 dim) = d losses[2] / d eemb, written whole (the
+ *     rows of entities that the batch does not touch are zero),
+ *   d_remb (n_relations x dim) = d losses[2] / d remb, written whole.
+ * No float atomics: every sum has a fixed order (per entity its (row, slot)
+ * samples ascending with the row's answer and anchor terms after the row's
+ * negatives; per relation its rows ascending), so a repeated call is bitwise
+ * equal.  Entity and relation ids must be in range (the caller's to check;
+ * the kernels clamp them, so that no access leaves the tables).
+ * Limits: n_rows (n_neg + 2) < 2^31 and 4 dim + n_neg + 1 <= 16320 (the row
+ * kernel's LDS); anything else, a null pointer or a non-positive size is
+ * RNNL_ERR_INVALID, decided before any HIP call.  scratch:
+ * rnnl_kge_rotate_step_scratch bytes.  Asynchronous on `stream`, capture-safe. */
+#define RNNL_KGE_TAIL 0
+#define RNNL_KGE_HEAD 1
+int rnnl_kge_sample_negatives(const int64_t *keys, const int64_t *offs, const int32_t *vals, int64_t n_keys,
+                              const int64_t *positives, int32_t n_rows, int32_t mode, int32_t n_entities,
+                              int32_t n_neg, uint64_t seed, int64_t step, int32_t *neg, int32_t *capped,
+                              void *stream);
+int rnnl_kge_rotate_step_scratch(int32_t n_rows, int32_t n_neg, int32_t n_entities, int32_t dim, size_t *bytes);
+int rnnl_kge_rotate_step(const float *eemb, const float *remb, int32_t n_entities, int32_t n_relations,
+                         int32_t dim, float gamma, const int64_t *positives, const int32_t *neg,
+                         const float *weights, int32_t n_rows, int32_t n_neg, int32_t mode, float alpha,
+                         void *scratch, size_t scratch_bytes, float *pos_score, float *neg_score, float *losses,
+                         float *d_eemb, float *d_remb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

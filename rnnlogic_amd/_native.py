@@ -20,6 +20,7 @@ ROTATE_DIRECT, ROTATE_MFMA = 0, 1
 FLAG_MIXED = 1
 ERR_COUNT_WIDTH, ERR_NODE_RANGE, ERR_ACC_RANGE = 8, 16, 32
 TOPK_MAX = 1024  # RNNL_TOPK_MAX
+KGE_TAIL, KGE_HEAD = 0, 1
 
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -139,6 +140,12 @@ SIGNATURES = [
     ("rnnl_predictorplus_backward", ctypes.c_int,
      [_P, _P, _P, _P, _I32, _P, _I32, _P, _P, _I64, _P, ctypes.c_size_t, _I32, _I32, _P, ctypes.c_size_t, _P,
       ctypes.c_size_t, _P, _P]),
+    ("rnnl_kge_sample_negatives", ctypes.c_int,
+     [_P, _P, _P, _I64, _P, _I32, _I32, _I32, _I32, ctypes.c_uint64, _I64, _P, _P, _P]),
+    ("rnnl_kge_rotate_step_scratch", ctypes.c_int, [_I32, _I32, _I32, _I32, ctypes.POINTER(ctypes.c_size_t)]),
+    ("rnnl_kge_rotate_step", ctypes.c_int,
+     [_P, _P, _I32, _I32, _I32, _F32, _P, _P, _P, _I32, _I32, _I32, _F32, _P, ctypes.c_size_t, _P, _P, _P, _P, _P,
+      _P]),
 ]
 
 

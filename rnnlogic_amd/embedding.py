@@ -73,8 +73,25 @@ class RotatE(torch.nn.Module):
         self.range = (self.gamma + 2.0) / self.emb_dim
         self.num_entities = cfg["nentity"]
         eemb = np.load(os.path.join(path, "entity_embedding.npy"), allow_pickle=False)
-        self.eemb = torch.nn.parameter.Parameter(torch.tensor(eemb))
         remb = torch.tensor(np.load(os.path.join(path, "relation_embedding.npy"), allow_pickle=False))
+        self._set_tables(torch.tensor(eemb), remb)
+
+    @classmethod
+    def from_tables(cls, eemb, remb, gamma):
+        """The scorer over tables that are already in memory (kge.RotatETrainer):
+        eemb (|E|, 2D), remb (nrel, D) without the inverse half; both are copied."""
+        self = cls.__new__(cls)
+        torch.nn.Module.__init__(self)
+        self.path = None
+        self.emb_dim = remb.size(1)
+        self.gamma = gamma
+        self.range = (self.gamma + 2.0) / self.emb_dim
+        self.num_entities = eemb.size(0)
+        self._set_tables(eemb.detach().clone(), remb.detach())
+        return self
+
+    def _set_tables(self, eemb, remb):
+        self.eemb = torch.nn.parameter.Parameter(eemb)
         self.remb = torch.nn.parameter.Parameter(torch.cat([remb, -remb], dim=0))
         self._tables = None
         self._ws = None
