@@ -648,6 +648,37 @@ int rnnl_miner_h_score(rnnl_miner m, const int32_t *order, int64_t begin, int64_
                        int32_t top_k, double h_temperature, double prior_weight, void *stream);
 int rnnl_miner_read(rnnl_miner m, double *weights, double *H, void *stream);
 
+/* ------------------------------------------- rule weights on held-out data --
+ * ReasoningPredictor::evaluate's per-triple work (rnnlogic.cpp:968-1043) with
+ * the rule lists and weights of the handle, on the handle's (train) graph.
+ *
+ *   rnnl_miner_set_weights: weights (device, n_rules doubles, list order:
+ *     relation 0's rules, then relation 1's, ...) replace the weights; the Adam
+ *     state of the rules is cleared, H and the rule lists stay.
+ *   rnnl_miner_evaluate: queries (device, n x 3 int32: h r t; need not be train
+ *     triples).  Per query, val[e] = sum over relation r's rules k in list
+ *     order of weight[k] * (double)(number of paths from h to e along rule k's
+ *     body), every edge equal to (h, r, t) skipped on every hop; fp64, product
+ *     then add, in list order per entity, so bitwise the reference's.  An
+ *     entity e is skipped when e != t and e is a known tail of (h, r):
+ *     known_keys (device, n_keys ascending int64 keys r * n_entities + h),
+ *     known_offs (device, n_keys + 1 int64), known_vals (device int32 tails,
+ *     ascending within a key); all three NULL: nothing is skipped.
+ *     ranks (device, n x 2 int32) receives num_g = the number of unskipped e
+ *     with val[e] > val[t] and num_ge = those with val[e] >= val[t]; t itself
+ *     always counts, so num_ge - num_g >= 1.  val (device, n x n_entities
+ *     doubles, or NULL) receives the val rows.  counters (device, 4 x uint64,
+ *     zeroed here): [1] != 0: a path count does not fit u32 (RNNL_ERR_RANGE
+ *     for the caller to raise), [2] != 0: a query with h, t or r out of range
+ *     (its ranks are 0 0, its val row is not written), [3]: internal.
+ *     Scratch for graphs of more than 512 entities is kept in the handle: one
+ *     evaluation per handle at a time.
+ * Both are asynchronous on `stream`. */
+int rnnl_miner_set_weights(rnnl_miner m, const double *weights, void *stream);
+int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const int64_t *known_keys,
+                        const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t *ranks,
+                        double *val, uint64_t *counters, void *stream);
+
 /* ------------------------------------------------------- training loss --
  * TrainerPredictor.train's loss (reference src/trainer.py:84-90) for a model
  * whose mask is all True (bias / RotatE features): with

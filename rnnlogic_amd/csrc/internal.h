@@ -112,6 +112,8 @@ struct rnnl_miner_s {
   std::vector<void *> rule_bufs;  // rule lists, parameters, scratch (rnnl_miner_set_rules)
   unsigned char *ground_scratch = nullptr, *chain_scratch = nullptr;
   int32_t ground_blocks = 0;
+  unsigned char *eval_scratch = nullptr;  // rnnl_miner_evaluate above its LDS regime; one of bufs
+  int32_t eval_blocks = 0;
 };
 
 struct rnnl_graph_s {

@@ -1,0 +1,303 @@
+// The reference miner's evaluation of its rule weights (SURVEY §8(f) f4,
+// DESIGN §3.10): ReasoningPredictor::evaluate_thread (miner/rnnlogic.cpp:
+// 968-1043) per query triple (h, r, t), on the miner handle's own graph and
+// with the rule lists and weights the handle holds.
+//
+//   val[e]  = sum over relation r's rules k, in list order, of
+//             wt[k] * (double)#paths(h -> e along the body), every edge equal
+//             to (h, r, t) skipped on every hop;
+//   num_g   = #{e unskipped : val[e] >  val[t]}
+//   num_ge  = #{e unskipped : val[e] >= val[t]}
+// where e is skipped when e != t and (h, r, e) is a known triple.
+//
+// One 256-thread workgroup per query, grid-stride; the queries are independent
+// once the weights are fixed.  Each of the four waves grounds one rule of a
+// round of four into integer scratch of its own (frontier list + dense u64
+// path counts per hop, integer atomics only, as ground_kernel of
+// mine_learn.hip); then the round's rules are added into the dense fp64 val
+// one after the other, in list order: product first, then the add, compiled
+// without contraction, no floating-point atomics (the destinations of one rule
+// are distinct).  So val is the reference's bit for bit.  Nothing is
+// materialised per (triple, rule, destination).
+//
+// Up to EVAL_LDS_E entities val and the integer scratch live in LDS (104 bytes
+// per entity, sized by the graph), above that in a per-workgroup global
+// scratch kept in the handle.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "internal.h"
+
+namespace rnnl {
+
+constexpr int EB = 256;          // threads per workgroup
+constexpr int EW = EB / 64;      // waves: rules grounded at once
+constexpr int EVAL_LDS_E = 512;  // everything in LDS up to this many entities (52 KiB)
+constexpr size_t EVAL_PER_E = 8 + EW * 24;  // val (f64) + per wave: counts A, B (u64), lists A, B (int)
+constexpr size_t EVAL_SCRATCH = 256u << 20;
+constexpr int EVAL_MAX_BLOCKS = 2048;
+
+enum : int { E_RANGE = 1, E_INVALID = 2, E_INTERNAL = 3 };
+
+struct EvalArgs {
+  const int32_t *queries;
+  int64_t n;
+  const int64_t *known_keys, *known_offs;
+  const int32_t *known_vals;
+  int64_t n_keys;
+  int32_t *ranks;
+  double *val_out;
+  unsigned char *scratch;
+  unsigned long long *flags;
+};
+
+namespace {
+
+__device__ __forceinline__ unsigned long long eval_ld_u64(unsigned long long *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// first index in [lo, hi) of the (relation, target)-sorted edges with relation >= r
+__device__ __forceinline__ int eval_edge_lower(const int32_t *rel, int lo, int hi, int r) {
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (rel[mid] < r)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+}  // namespace
+
+template <bool SMALL>
+__global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, EvalArgs a) {
+  extern __shared__ unsigned long long eval_smem[];
+  __shared__ int s_n[EW], s_na[EW], s_g[EW], s_ge[EW];
+  const int E = d.E, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  unsigned char *base = SMALL ? reinterpret_cast<unsigned char *>(eval_smem)
+                              : a.scratch + (size_t)blockIdx.x * EVAL_PER_E * (size_t)E;
+  double *val = reinterpret_cast<double *>(base);
+  unsigned char *ints = base + 8 * (size_t)E;  // wave w: counts A, counts B (u64 x E), list A, list B (int x E)
+  if (SMALL) {  // the global scratch is zeroed when it is allocated and left zeroed by every query
+    for (int i = tid; i < EW * 2 * E; i += EB) {
+      const int w = i / (2 * E);
+      reinterpret_cast<unsigned long long *>(ints + (size_t)w * 24 * (size_t)E)[i - w * 2 * E] = 0ull;
+    }
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int64_t qi = blockIdx.x; qi < a.n; qi += gridDim.x) {
+    const int h = a.queries[3 * qi], r = a.queries[3 * qi + 1], t = a.queries[3 * qi + 2];
+    if ((unsigned)h >= (unsigned)E || (unsigned)t >= (unsigned)E || (unsigned)r >= (unsigned)d.R) {
+      if (tid == 0) {
+        atomicOr(&a.flags[E_INVALID], 1ull);
+        a.ranks[2 * qi] = 0;
+        a.ranks[2 * qi + 1] = 0;
+      }
+      continue;
+    }
+    for (int x = tid; x < E; x += EB) val[x] = 0.0;
+    const int rb = l.rule_off[r], nr = l.rule_off[r + 1] - rb;
+    bool wide = false;
+#pragma unroll 1
+    for (int jb = 0; jb < nr; jb += EW) {
+      const int nw = min(EW, nr - jb);  // rules of this round
+      int mx = 0;
+      for (int w = 0; w < nw; ++w) mx = max(mx, l.rule_len[rb + jb + w]);
+      const int rule = rb + jb + wid;
+      const int len = wid < nw ? l.rule_len[rule] : 0;
+      unsigned long long *ca = reinterpret_cast<unsigned long long *>(ints + (size_t)wid * 24 * (size_t)E);
+      unsigned long long *cb = ca + E;
+      int *la = reinterpret_cast<int *>(cb + E), *lb = la + E;
+      int na = 0;
+      if (len > 0) {
+        if (lane == 0) {
+          la[0] = h;
+          ca[h] = 1;
+        }
+        na = 1;
+      }
+      for (int k = 0; k < mx; ++k) {
+        const bool act = k < len;
+        if (act && lane == 0) s_n[wid] = 0;
+        __syncthreads();
+        if (act) {
+          const int rel = l.rule_body[3 * rule + k];
+          for (int i = lane; i < na; i += 64) {
+            const int e = la[i];
+            const unsigned long long n = eval_ld_u64(&ca[e]);
+            const int en = d.out_off[e + 1];
+            for (int b = eval_edge_lower(l.so_rel, d.out_off[e], en, rel); b < en && l.so_rel[b] == rel; ++b) {
+              const int x = l.so_dst[b];
+              if (e == h && rel == r && x == t) continue;  // the query's own edge, and every copy of it
+              wide |= n > 0xffffffffull;  // the paths through here alone are past 32 bits
+              if (atomicAdd(&cb[x], n) == 0) lb[atomicAdd(&s_n[wid], 1)] = x;
+            }
+          }
+        }
+        __syncthreads();
+        if (act) {
+          for (int i = lane; i < na; i += 64) ca[la[i]] = 0;
+          na = s_n[wid];
+          unsigned long long *tc = ca;
+          ca = cb;
+          cb = tc;
+          int *tl = la;
+          la = lb;
+          lb = tl;
+        }
+      }
+      if (lane == 0) s_na[wid] = na;
+      __syncthreads();
+      // the round's rules into val, one after the other: list order per destination
+      for (int w = 0; w < nw; ++w) {
+        const int len2 = l.rule_len[rb + jb + w];
+        if (len2 == 0) continue;  // an empty body reaches nothing
+        const double wt = l.wt[rb + jb + w];
+        unsigned long long *c0 = reinterpret_cast<unsigned long long *>(ints + (size_t)w * 24 * (size_t)E);
+        int *l0 = reinterpret_cast<int *>(c0 + 2 * (size_t)E);
+        unsigned long long *fc = (len2 & 1) ? c0 + E : c0;  // one swap per hop
+        const int *fl = (len2 & 1) ? l0 + E : l0;
+        const int n2 = s_na[w];
+        for (int i = tid; i < n2; i += EB) {
+          const int x = fl[i];
+          const unsigned long long c = eval_ld_u64(&fc[x]);
+          wide |= c > 0xffffffffull;
+          const double term = wt * (double)c;
+          val[x] = val[x] + term;
+          fc[x] = 0;
+        }
+        __syncthreads();
+      }
+    }
+    if (wide) atomicOr(&a.flags[E_RANGE], 1ull);
+    __syncthreads();
+    const double t_val = val[t];
+    int g = 0, ge = 0;
+    for (int x = tid; x < E; x += EB) {
+      const double v = val[x];
+      if (a.val_out) a.val_out[qi * (int64_t)E + x] = v;
+      if (x != t) {
+        g += v > t_val;
+        ge += v >= t_val;
+      }
+    }
+    if (a.known_keys) {  // minus the other known tails of (h, r)
+      const int64_t key = (int64_t)r * E + h;
+      int64_t lo = 0, hi = a.n_keys;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a.known_keys[mid] < key)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      if (lo < a.n_keys && a.known_keys[lo] == key) {
+        const int64_t b0 = a.known_offs[lo], b1 = a.known_offs[lo + 1];
+        for (int64_t i = b0 + tid; i < b1; i += EB) {
+          const int e = a.known_vals[i];
+          if ((unsigned)e >= (unsigned)E || e == t || (i > b0 && a.known_vals[i - 1] == e)) continue;
+          const double v = val[e];
+          g -= v > t_val;
+          ge -= v >= t_val;
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      g += __shfl_down(g, o, 64);
+      ge += __shfl_down(ge, o, 64);
+    }
+    if (lane == 0) {
+      s_g[wid] = g;
+      s_ge[wid] = ge;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int sg = 0, sge = 1;  // the tail itself always counts
+      for (int w = 0; w < EW; ++w) {
+        sg += s_g[w];
+        sge += s_ge[w];
+      }
+      a.ranks[2 * qi] = sg;
+      a.ranks[2 * qi + 1] = sge;
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace rnnl
+
+using namespace rnnl;
+
+extern "C" {
+
+int rnnl_miner_set_weights(rnnl_miner m, const double *weights, void *stream) {
+  if (!m || !m->l.rule_off || (m->l.n_rules > 0 && !weights)) {
+    set_error("rnnl_miner_set_weights: bad arguments (set the rules first)");
+    return RNNL_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = (size_t)m->l.n_rules * 8;
+  if (bytes) {
+    RNNL_HIP_CHECK(hipMemcpyAsync(m->l.wt, weights, bytes, hipMemcpyDeviceToDevice, st));
+    RNNL_HIP_CHECK(hipMemsetAsync(m->l.am, 0, 3 * bytes, st));  // am, av, at are contiguous
+  }
+  return RNNL_OK;
+}
+
+int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const int64_t *known_keys,
+                        const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t *ranks,
+                        double *val, uint64_t *counters, void *stream) {
+  const bool none = !known_keys && !known_offs && !known_vals;
+  const bool all = known_keys && known_offs && known_vals && n_keys >= 0;
+  if (!m || !m->l.rule_off || n < 0 || (n > 0 && (!queries || !ranks)) || !counters || !(none || all)) {
+    set_error("rnnl_miner_evaluate: bad arguments (set the rules first; the known-tail arrays all or none)");
+    return RNNL_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  RNNL_HIP_CHECK(hipMemsetAsync(counters, 0, 4 * 8, st));
+  if (n == 0) return RNNL_OK;
+  EvalArgs a = {};
+  a.queries = queries;
+  a.n = n;
+  if (all && n_keys > 0) {
+    a.known_keys = known_keys;
+    a.known_offs = known_offs;
+    a.known_vals = known_vals;
+    a.n_keys = n_keys;
+  }
+  a.ranks = ranks;
+  a.val_out = val;
+  a.flags = reinterpret_cast<unsigned long long *>(counters);
+  const size_t E = (size_t)m->d.E;
+  if (m->d.E <= EVAL_LDS_E) {
+    const unsigned grid = (unsigned)std::min<int64_t>(n, EVAL_MAX_BLOCKS);
+    hipLaunchKernelGGL(eval_kernel<true>, dim3(grid), dim3(EB), EVAL_PER_E * E, st, m->d, m->l, a);
+  } else {
+    if (!m->eval_scratch) {  // workgroups bounded by their scratch; zeroed once, every query leaves it zeroed
+      const int32_t blocks =
+          (int32_t)std::max<size_t>(16, std::min<size_t>(EVAL_MAX_BLOCKS, EVAL_SCRATCH / (EVAL_PER_E * E)));
+      void *p = nullptr;
+      if (hipMalloc(&p, (size_t)blocks * EVAL_PER_E * E) != hipSuccess) {
+        set_error("rnnl_miner_evaluate: device allocation failed");
+        return RNNL_ERR_NOMEM;
+      }
+      m->bufs.push_back(p);
+      RNNL_HIP_CHECK(hipMemset(p, 0, (size_t)blocks * EVAL_PER_E * E));
+      RNNL_HIP_CHECK(hipDeviceSynchronize());
+      m->eval_scratch = static_cast<unsigned char *>(p);
+      m->eval_blocks = blocks;
+    }
+    a.scratch = m->eval_scratch;
+    const unsigned grid = (unsigned)std::min<int64_t>(n, m->eval_blocks);
+    hipLaunchKernelGGL(eval_kernel<false>, dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
+  }
+  RNNL_HIP_CHECK(hipGetLastError());
+  return RNNL_OK;
+}
+
+}  // extern "C"

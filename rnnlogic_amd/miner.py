@@ -15,7 +15,13 @@ running mean (RuleGenerator::update) and the rule file (out_rules)
     miner.set_logic_rules(rel2rules)    # or step by step, as ReasoningPredictor
     miner.learn(lr, wd, temp); miner.h_score(top_k); miner.weights(); miner.H()
 
+    miner.set_weights(rel2weights)      # or read_rules("mined_rules.txt"): rules + weights from a file
+    miner.evaluate("test")              # dict(mr, mrr, hit1, hit3, hit10, n), as ReasoningPredictor::evaluate
+    miner.eval_ranks(triples); miner.scores(triples)   # the (num_g, num_ge) pairs / the val rows behind it
+
     python -m rnnlogic_amd.miner -data-path D -output-file F -max-length 3 ...   # main.cpp's flags
+    python -m rnnlogic_amd.miner -data-path D -output-file F ... -evaluate both  # + one metrics line per split
+    python -m rnnlogic_amd.miner -data-path D -rule-file F -evaluate test        # evaluate a rule file, no mining
 
 The pool equals the reference's for the same train graph: every relation
 path of length <= max_length from h to t of a train triple (h, r, t), the
@@ -30,13 +36,114 @@ seeded numpy generators, or given (`orders`, `selections`) to replay a
 reference run.  Where the reference leaves ties to std::sort they are defined
 here: top-k by val descending then position in the rule list, out_rules by H
 descending then pool order.
+
+evaluate (ReasoningPredictor::evaluate, rnnlogic.cpp:968-1120) ranks the tail
+of held-out triples by sum_k wt[k] * #paths on the train graph with the
+triple's own edge removed (rnnl_miner_evaluate, csrc/mine_eval.hip).  The
+scores are the reference's bit for bit (fp64, product then add, rule list
+order per entity) and the two counts per triple — entities scoring above the
+tail, and at least as high — are exact, so the expectation over the tie run
+gives the reference's MR / MRR / HITS.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
 
 from . import _native
+
+
+def flatten_weights(rule_off, rel2weights):
+    """One float64 sequence per relation, of the lengths of the rule lists
+    (rule_off: R + 1 offsets) -> the flat float64 array in list order."""
+    R = len(rule_off) - 1
+    if len(rel2weights) != R:
+        raise ValueError("set_weights: one weight sequence per relation expected (%d, got %d)"
+                         % (R, len(rel2weights)))
+    flat = np.zeros(int(rule_off[-1]), dtype=np.float64)
+    for r, w in enumerate(rel2weights):
+        w = np.asarray(w, dtype=np.float64).reshape(-1)
+        if len(w) != int(rule_off[r + 1] - rule_off[r]):
+            raise ValueError("set_weights: relation %d has %d rules, got %d weights"
+                             % (r, int(rule_off[r + 1] - rule_off[r]), len(w)))
+        if not np.all(np.isfinite(w)):
+            raise ValueError("set_weights: a weight of relation %d is not finite" % r)
+        flat[int(rule_off[r]):int(rule_off[r + 1])] = w
+    return flat
+
+
+def read_rule_file(file_name, n_relations):
+    """A rule file of 'head body... x' lines (out_rules / mined_rules.txt) ->
+    (rel2rules, rel2weights) in file order per head.  A last token that is not
+    an integer is x, the weight; a line of integers alone has weight 0."""
+    rel2rules = [[] for _ in range(n_relations)]
+    rel2weights = [[] for _ in range(n_relations)]
+    with open(file_name) as fi:
+        for no, line in enumerate(fi, 1):
+            tok = line.split()
+            if not tok:
+                continue
+            x = 0.0
+            try:
+                int(tok[-1])
+            except ValueError:
+                try:
+                    x = float(tok[-1])
+                except ValueError:
+                    raise ValueError("%s:%d: %r is not a number" % (file_name, no, tok[-1]))
+                tok = tok[:-1]
+            try:
+                ids = [int(v) for v in tok]
+            except ValueError:
+                raise ValueError("%s:%d: relation ids must be integers" % (file_name, no))
+            if not ids:
+                raise ValueError("%s:%d: no head relation" % (file_name, no))
+            if any(v < 0 or v >= n_relations for v in ids):
+                raise ValueError("%s:%d: relation id out of range [0, %d)" % (file_name, no, n_relations))
+            if len(ids) > 4:
+                raise ValueError("%s:%d: rule bodies have at most 3 relations" % (file_name, no))
+            if not math.isfinite(x):
+                raise ValueError("%s:%d: the weight is not finite" % (file_name, no))
+            rel2rules[ids[0]].append((ids[0], tuple(ids[1:])))
+            rel2weights[ids[0]].append(x)
+    return rel2rules, rel2weights
+
+
+def expectation_metrics(ranks, n_entities):
+    """ReasoningPredictor::evaluate's metrics (rnnlogic.cpp:1070-1116) of
+    (num_g, num_ge) pairs: the true tail is equally likely at every rank of
+    its tie run num_g + 1 .. num_ge, so each metric is the mean of its table
+    over the run — cumulative tables, then one sum in triple order, in fp64 as
+    the reference.  Returns dict(mr, mrr, hit1, hit3, hit10, n)."""
+    ranks = np.asarray(ranks, dtype=np.int64).reshape(-1, 2)
+    if len(ranks) == 0:
+        raise ValueError("expectation_metrics: no ranks")
+    E = int(n_entities)
+    if np.any(ranks[:, 0] < 0) or np.any(ranks[:, 1] <= ranks[:, 0]) or np.any(ranks[:, 1] > E):
+        raise ValueError("expectation_metrics: pairs must satisfy 0 <= num_g < num_ge <= n_entities")
+    t_mr, t_mrr, t_h1, t_h3, t_h10 = ([0.0] * (E + 1) for _ in range(5))
+    for rank in range(1, E + 1):
+        t_mr[rank] = float(rank) + t_mr[rank - 1]
+        t_mrr[rank] = 1.0 / rank + t_mrr[rank - 1]
+        t_h1[rank] = (1.0 if rank <= 1 else 0.0) + t_h1[rank - 1]
+        t_h3[rank] = (1.0 if rank <= 3 else 0.0) + t_h3[rank - 1]
+        t_h10[rank] = (1.0 if rank <= 10 else 0.0) + t_h10[rank - 1]
+    mr = mrr = hit1 = hit3 = hit10 = 0.0
+    for g, ge in ranks.tolist():
+        run = float(ge - g)
+        mr += (t_mr[ge] - t_mr[g]) / run
+        mrr += (t_mrr[ge] - t_mrr[g]) / run
+        hit1 += (t_h1[ge] - t_h1[g]) / run
+        hit3 += (t_h3[ge] - t_h3[g]) / run
+        hit10 += (t_h10[ge] - t_h10[g]) / run
+    n = float(len(ranks))
+    return dict(mr=mr / n, mrr=mrr / n, hit1=hit1 / n, hit3=hit3 / n, hit10=hit10 / n, n=len(ranks))
+
+
+def metrics_line(name, m):
+    return "%s | MR %.6f MRR %.6f HITS@1 %.6f @3 %.6f @10 %.6f" % (name, m["mr"], m["mrr"], m["hit1"], m["hit3"],
+                                                                  m["hit10"])
 
 
 class RuleMiner(object):
@@ -61,6 +168,7 @@ class RuleMiner(object):
         self.pool, self.pool_H = None, None
         self.chunk_triples = None     # triples per grounding chunk; None: as many as budget_bytes allows
         self.budget_bytes = 1 << 30   # device memory for one chunk's (triple, rule, destination, count) entries
+        self._known = None            # known tails over train + valid + test (eval_ranks), built once
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -260,6 +368,83 @@ class RuleMiner(object):
         """Per relation, the H score of each rule of its list (float64)."""
         return self._read(1)
 
+    # ------------------------------------------------------------ evaluation
+    def set_weights(self, rel2weights):
+        """rel2weights[r][k] (float64) becomes the weight of rule k of relation
+        r's current list; the rules' Adam state is cleared, H stays."""
+        flat = flatten_weights(self._rule_off, rel2weights)
+        with torch.cuda.device(self.device):
+            dev = torch.from_numpy(flat).to(self.device)
+            _native.call("rnnl_miner_set_weights", self._handle, dev.data_ptr(),
+                         torch.cuda.current_stream(self.device).cuda_stream)
+            torch.cuda.current_stream(self.device).synchronize()  # dev is released on return
+
+    def read_rules(self, file_name):
+        """Sets the rules of a 'head body... x' file (out_rules /
+        mined_rules.txt), in file order per head, with x as the weight.
+        Returns the number of rules read."""
+        rel2rules, rel2weights = read_rule_file(file_name, self.graph.relation_size)
+        self.set_logic_rules(rel2rules)
+        self.set_weights(rel2weights)
+        return sum(len(x) for x in rel2rules)
+
+    def _queries(self, triples):
+        q = np.ascontiguousarray(np.asarray(triples, dtype=np.int64).reshape(-1, 3))
+        E, R = self.graph.entity_size, self.graph.relation_size
+        if len(q) and (q.min() < 0 or q[:, 0].max() >= E or q[:, 2].max() >= E or q[:, 1].max() >= R):
+            raise ValueError("query triple out of range")
+        return q.astype(np.int32)
+
+    def _known_tails(self):
+        if self._known is None:
+            from .data import _DeviceLists
+            from .kge import true_answers
+            every = [np.asarray(getattr(self.graph, name, None) or [], dtype=np.int64).reshape(-1, 3)
+                     for name in ("train_facts", "valid_facts", "test_facts")]
+            self._known = _DeviceLists(true_answers(np.concatenate(every), self.graph.entity_size, "tail"),
+                                       self.device)
+        return self._known
+
+    @torch.no_grad()
+    def _evaluate(self, triples, filtered, want_val):
+        q = self._queries(triples)
+        n, E = len(q), self.graph.entity_size
+        with torch.cuda.device(self.device):
+            qd = torch.from_numpy(q).to(self.device)
+            ranks = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
+            val = torch.zeros((n, E), dtype=torch.float64, device=self.device) if want_val else None
+            k = self._known_tails() if filtered else None
+            _native.call("rnnl_miner_evaluate", self._handle, qd.data_ptr(), n,
+                         k.keys.data_ptr() if k else None, k.offs.data_ptr() if k else None,
+                         k.vals.data_ptr() if k else None, k.keys.numel() if k else 0, ranks.data_ptr(),
+                         val.data_ptr() if want_val else None, self._counters.data_ptr(),
+                         torch.cuda.current_stream(self.device).cuda_stream)
+            self._check_counters()
+        return ranks, val
+
+    def scores(self, triples):
+        """(n, |E|) float64 on the device: per query (h, r, t) the val of every
+        entity — sum over r's rules of weight * path count from h, the triple's
+        own edge removed — bitwise what the reference computes."""
+        return self._evaluate(triples, False, True)[1]
+
+    def eval_ranks(self, triples, filtered=True):
+        """(n, 2) numpy int64: per query (num_g, num_ge), the entities scoring
+        above the true tail / at least as high (the tail included).  filtered:
+        the other known tails of (h, r) over train, valid and test are left
+        out (a graph without valid_facts / test_facts filters by train)."""
+        return self._evaluate(triples, filtered, False)[0].cpu().numpy().astype(np.int64)
+
+    def evaluate(self, split="test", triples=None, filtered=True):
+        """ReasoningPredictor::evaluate over graph.valid_facts / test_facts
+        (split 'valid' / 'test') or the given triples, with the current rules
+        and weights: dict(mr, mrr, hit1, hit3, hit10, n)."""
+        if triples is None:
+            if split not in ("valid", "test"):
+                raise ValueError("evaluate: split must be 'valid' or 'test'")
+            triples = getattr(self.graph, split + "_facts")
+        return expectation_metrics(self.eval_ranks(triples, filtered), self.graph.entity_size)
+
     def mine(self, max_length, iterations, top_n, top_k, lr, wd, temp, top_n_out=0, seed=0, orders=None,
              selections=None, portion=1.0):
         """The reference miner's main loop (miner/main.cpp:27-49): search, then
@@ -335,7 +520,7 @@ def main(argv=None):
     from .data import KnowledgeGraph
     ap = argparse.ArgumentParser(prog="python -m rnnlogic_amd.miner", allow_abbrev=False)
     ap.add_argument("-data-path", dest="data_path", required=True)
-    ap.add_argument("-output-file", dest="output_file", required=True)
+    ap.add_argument("-output-file", dest="output_file", default=None)
     ap.add_argument("-max-length", dest="max_length", type=int, default=2)
     ap.add_argument("-threads", dest="threads", type=int, default=1)
     ap.add_argument("-iterations", dest="iterations", type=int, default=10)
@@ -346,10 +531,21 @@ def main(argv=None):
     ap.add_argument("-top-n", dest="top_n", type=int, default=100)
     ap.add_argument("-top-n-out", dest="top_n_out", type=int, default=100)
     ap.add_argument("-seed", dest="seed", type=int, default=0)
+    ap.add_argument("-evaluate", dest="evaluate", choices=["valid", "test", "both"], default=None)
+    ap.add_argument("-rule-file", dest="rule_file", default=None)
     a = ap.parse_args(argv)
+    if a.output_file is None and a.rule_file is None:
+        ap.error("the following arguments are required: -output-file")
+    if a.rule_file is not None and (a.output_file is not None or a.evaluate is None):
+        ap.error("-rule-file evaluates a rule file: give -evaluate, and no -output-file")
     miner = RuleMiner(KnowledgeGraph(a.data_path))
-    miner.mine(a.max_length, a.iterations, a.top_n, a.top_k, a.lr, a.wd, a.temp, a.top_n_out, seed=a.seed)
-    print("#Rules written: %d" % miner.out_rules(a.output_file, a.top_n_out))
+    if a.output_file is not None:
+        miner.mine(a.max_length, a.iterations, a.top_n, a.top_k, a.lr, a.wd, a.temp, a.top_n_out, seed=a.seed)
+        print("#Rules written: %d" % miner.out_rules(a.output_file, a.top_n_out))
+    else:  # evaluate a rule file: no search, no learn
+        print("#Rules read: %d" % miner.read_rules(a.rule_file))
+    for split in {None: (), "both": ("valid", "test")}.get(a.evaluate, (a.evaluate,)):
+        print(metrics_line(split.capitalize(), miner.evaluate(split)))
 
 
 if __name__ == "__main__":
