@@ -596,6 +596,29 @@ int rnnl_miner_destroy(rnnl_miner m);
 int rnnl_rule_search(rnnl_miner m, int32_t max_length, uint64_t *table, int64_t table_cap, uint64_t *rules_out,
                      int64_t out_cap, uint64_t *counters, void *stream);
 
+/* Bodies of up to five relations (max_length 1..5), the reference's
+ * semantics throughout: a triple with h == t gives exactly one rule without
+ * a body (length 0) and nothing else (rnnl_rule_search walks on from such a
+ * triple; it is left as it is).  Lengths 4 and 5 are the exact join, on the
+ * middle entity, of the forward paths from h (depth 2 / 3, streamed) with the
+ * length-2 suffixes into t; nothing is enumerated at deg^max_length.
+ *   rnnl_rule_key_bits: bits = max(1, ceil(log2 n_relations)) per relation of a
+ *     long key, or RNNL_ERR_INVALID (the message names the bound) unless
+ *     3 + (max_length + 1) * bits <= 64: at most 1,024 relations at
+ *     max_length 5, 4,096 at 4.  Host only.
+ *   rnnl_rule_search_long: table / rules_out / counters as rnnl_rule_search.
+ *     Keys are head | len (3 bits) | b1 .. b_max_length with `bits` per
+ *     relation, bodies left-aligned and zero-padded: (head << 3 | len) <<
+ *     (max_length * bits) | b1 << ((max_length - 1) * bits) | ...; numeric
+ *     order == the reference's order (head, length, body).  suffix_cap
+ *     (0 = 2,048, the most) bounds the length-2 suffixes of a tail kept sorted
+ *     in LDS; a tail with more is searched edge by edge instead, with the same
+ *     result: no capacity of the kernel truncates the pool.  Arguments,
+ *     the key bound included, are checked before any device call. */
+int rnnl_rule_key_bits(int32_t n_relations, int32_t max_length, int32_t *bits);
+int rnnl_rule_search_long(rnnl_miner m, int32_t max_length, int32_t suffix_cap, uint64_t *table, int64_t table_cap,
+                          uint64_t *rules_out, int64_t out_cap, uint64_t *counters, void *stream);
+
 /* ------------------------------------------ rule weights and H scores --
  * What the reference miner does after its search (miner/main.cpp:40-48): one
  * weight per rule learned by online Adam over the train triples
@@ -634,6 +657,11 @@ int rnnl_rule_search(rnnl_miner m, int32_t max_length, uint64_t *table, int64_t 
  * All but set_rules are asynchronous on `stream`. */
 int rnnl_miner_set_rules(rnnl_miner m, const int32_t *rule_off, const int32_t *rule_len, const int32_t *rule_body,
                          const double *prior);
+/* As rnnl_miner_set_rules with bodies of length 0..5: rule i has body
+ * rule_body[5 i .. 5 i + rule_len[i]).  The handle stores five relations per
+ * rule either way; learn, H score and evaluation walk a body hop by hop. */
+int rnnl_miner_set_rules_long(rnnl_miner m, const int32_t *rule_off, const int32_t *rule_len,
+                              const int32_t *rule_body, const double *prior);
 int rnnl_miner_ground_count(rnnl_miner m, const int32_t *order, int64_t begin, int64_t count,
                             const int64_t *pair_base, int64_t n_pairs, int64_t *pair_off, uint64_t *counters,
                             void *stream);

@@ -104,7 +104,10 @@ SIGNATURES = [
     ("rnnl_miner_create", ctypes.c_int, [_P, _I64, _I32, _I32, _P]),
     ("rnnl_miner_destroy", ctypes.c_int, [_P]),
     ("rnnl_rule_search", ctypes.c_int, [_P, _I32, _P, _I64, _P, _I64, _P, _P]),
+    ("rnnl_rule_key_bits", ctypes.c_int, [_I32, _I32, _P]),
+    ("rnnl_rule_search_long", ctypes.c_int, [_P, _I32, _I32, _P, _I64, _P, _I64, _P, _P]),
     ("rnnl_miner_set_rules", ctypes.c_int, [_P, _P, _P, _P, _P]),
+    ("rnnl_miner_set_rules_long", ctypes.c_int, [_P, _P, _P, _P, _P]),
     ("rnnl_miner_ground_count", ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, _P, _P]),
     ("rnnl_miner_ground_fill", ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P]),
     ("rnnl_miner_learn", ctypes.c_int,

@@ -43,12 +43,14 @@ struct MinerDev {
 // What the miner's learn / H_score stage adds to the handle (mine_learn.hip):
 // the out-edges once more, sorted by (source, relation, target) under the same
 // out_off, the current rule lists and one Adam parameter + H per rule.
+constexpr int RULE_STRIDE = 5;  // body relations stored per rule: the longest body
+
 struct MinerLearnDev {
   const int32_t *so_rel = nullptr, *so_dst = nullptr;  // n, n
   int32_t n_rules = 0;
   const int32_t *rule_off = nullptr;   // R + 1: relation r's rules are [rule_off[r], rule_off[r + 1])
-  const int32_t *rule_len = nullptr;   // n_rules, 0..3
-  const int32_t *rule_body = nullptr;  // n_rules x 3
+  const int32_t *rule_len = nullptr;   // n_rules, 0..RULE_STRIDE
+  const int32_t *rule_body = nullptr;  // n_rules x RULE_STRIDE
   const double *prior = nullptr;       // n_rules
   double *wt = nullptr, *am = nullptr, *av = nullptr, *at = nullptr, *H = nullptr, *val = nullptr;  // n_rules
 };

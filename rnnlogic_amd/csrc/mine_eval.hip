@@ -125,7 +125,7 @@ __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, E
         if (act && lane == 0) s_n[wid] = 0;
         __syncthreads();
         if (act) {
-          const int rel = l.rule_body[3 * rule + k];
+          const int rel = l.rule_body[RULE_STRIDE * rule + k];
           for (int i = lane; i < na; i += 64) {
             const int e = la[i];
             const unsigned long long n = eval_ld_u64(&ca[e]);

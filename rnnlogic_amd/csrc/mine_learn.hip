@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <string>
 #include <vector>
 
 #include "internal.h"
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(GB) void ground_kernel(MinerDev d, MinerLearnDev l,
     }
     __syncthreads();
     for (int k = 0; k < len; ++k) {
-      const int rel = l.rule_body[3 * rule + k];
+      const int rel = l.rule_body[RULE_STRIDE * rule + k];
       if (tid == 0) s_n = 0;
       __syncthreads();
       for (int i = tid; i < na; i += GB) {
@@ -505,34 +506,38 @@ bool chunk_args_ok(rnnl_miner m, const int32_t *order, int64_t begin, int64_t co
 
 extern "C" {
 
-int rnnl_miner_set_rules(rnnl_miner m, const int32_t *rule_off, const int32_t *rule_len, const int32_t *rule_body,
-                         const double *prior) {
+// stride: relations per rule in the caller's rule_body (3 or RULE_STRIDE); max_len: the longest body it may hold
+static int set_rules_impl(rnnl_miner m, const int32_t *rule_off, const int32_t *rule_len, const int32_t *rule_body,
+                          const double *prior, int stride, int max_len, const std::string &who) {
   if (!m || !rule_off || rule_off[0] != 0) {
-    set_error("rnnl_miner_set_rules: bad arguments");
+    set_error(who + ": bad arguments");
     return RNNL_ERR_INVALID;
   }
   const int R = m->d.R, E = m->d.E;
   for (int r = 0; r < R; ++r)
     if (rule_off[r + 1] < rule_off[r]) {
-      set_error("rnnl_miner_set_rules: rule_off must not decrease");
+      set_error(who + ": rule_off must not decrease");
       return RNNL_ERR_INVALID;
     }
   const int32_t n = rule_off[R];
   if (n > 0 && (!rule_len || !rule_body)) {
-    set_error("rnnl_miner_set_rules: rule_len / rule_body missing");
+    set_error(who + ": rule_len / rule_body missing");
     return RNNL_ERR_INVALID;
   }
   for (int32_t i = 0; i < n; ++i) {
-    if (rule_len[i] < 0 || rule_len[i] > 3) {
-      set_error("rnnl_miner_set_rules: body length must be 0..3");
+    if (rule_len[i] < 0 || rule_len[i] > max_len) {
+      set_error(who + ": body length must be 0.." + std::to_string(max_len));
       return RNNL_ERR_INVALID;
     }
     for (int k = 0; k < rule_len[i]; ++k)
-      if (rule_body[3 * i + k] < 0 || rule_body[3 * i + k] >= R) {
-        set_error("rnnl_miner_set_rules: body relation out of range");
+      if (rule_body[(size_t)stride * i + k] < 0 || rule_body[(size_t)stride * i + k] >= R) {
+        set_error(who + ": body relation out of range");
         return RNNL_ERR_INVALID;
       }
   }
+  std::vector<int32_t> packed((size_t)n * RULE_STRIDE, 0);  // the handle's storage: RULE_STRIDE per rule
+  for (int32_t i = 0; i < n; ++i)
+    for (int k = 0; k < rule_len[i]; ++k) packed[(size_t)RULE_STRIDE * i + k] = rule_body[(size_t)stride * i + k];
   RNNL_HIP_CHECK(hipDeviceSynchronize());  // earlier work may still read the old lists
   for (void *p : m->rule_bufs) (void)hipFree(p);
   m->rule_bufs.clear();
@@ -546,19 +551,19 @@ int rnnl_miner_set_rules(rnnl_miner m, const int32_t *rule_off, const int32_t *r
   void *p_off, *p_len, *p_body, *p_prior, *p_state, *p_gs, *p_cs;
   int rc = dev_alloc(m, (size_t)(R + 1) * 4, &p_off);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 4, &p_len);
-  if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 12, &p_body);
+  if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 4 * RULE_STRIDE, &p_body);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 8, &p_prior);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 8 * 6, &p_state);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)m->ground_blocks * 24 * (size_t)E, &p_gs);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)R * 16 * (size_t)E, &p_cs);
   if (rc != RNNL_OK) {
-    set_error("rnnl_miner_set_rules: device allocation failed");
+    set_error(who + ": device allocation failed");
     return rc;
   }
   RNNL_HIP_CHECK(hipMemcpy(p_off, rule_off, (size_t)(R + 1) * 4, hipMemcpyHostToDevice));
   if (n > 0) {
     RNNL_HIP_CHECK(hipMemcpy(p_len, rule_len, (size_t)n * 4, hipMemcpyHostToDevice));
-    RNNL_HIP_CHECK(hipMemcpy(p_body, rule_body, (size_t)n * 12, hipMemcpyHostToDevice));
+    RNNL_HIP_CHECK(hipMemcpy(p_body, packed.data(), (size_t)n * 4 * RULE_STRIDE, hipMemcpyHostToDevice));
     if (prior)
       RNNL_HIP_CHECK(hipMemcpy(p_prior, prior, (size_t)n * 8, hipMemcpyHostToDevice));
     else
@@ -580,6 +585,17 @@ int rnnl_miner_set_rules(rnnl_miner m, const int32_t *rule_off, const int32_t *r
   m->ground_scratch = static_cast<unsigned char *>(p_gs);
   m->chain_scratch = static_cast<unsigned char *>(p_cs);
   return RNNL_OK;
+}
+
+int rnnl_miner_set_rules(rnnl_miner m, const int32_t *rule_off, const int32_t *rule_len, const int32_t *rule_body,
+                         const double *prior) {
+  return set_rules_impl(m, rule_off, rule_len, rule_body, prior, 3, 3, "rnnl_miner_set_rules");
+}
+
+int rnnl_miner_set_rules_long(rnnl_miner m, const int32_t *rule_off, const int32_t *rule_len,
+                              const int32_t *rule_body, const double *prior) {
+  return set_rules_impl(m, rule_off, rule_len, rule_body, prior, RULE_STRIDE, RULE_STRIDE,
+                        "rnnl_miner_set_rules_long");
 }
 
 int rnnl_miner_ground_count(rnnl_miner m, const int32_t *order, int64_t begin, int64_t count,

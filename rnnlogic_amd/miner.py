@@ -5,7 +5,7 @@ csrc/mine.hip), then one weight per rule learned by online Adam
 running mean (RuleGenerator::update) and the rule file (out_rules)
 (rnnl_miner_learn / rnnl_miner_h_score, csrc/mine_learn.hip).
 
-    miner = RuleMiner(graph)            # graph: rnnlogic_amd.data.KnowledgeGraph
+    miner = RuleMiner(graph)            # graph: rnnlogic_amd.data.KnowledgeGraph; max_body=5: bodies up to 5
     rules = miner.search(max_length=3)  # [(head, body tuple)] in the reference's order
     miner.save("pool.txt")              # "type head body... H wt prior", as RuleMiner::save
 
@@ -19,14 +19,20 @@ running mean (RuleGenerator::update) and the rule file (out_rules)
     miner.evaluate("test")              # dict(mr, mrr, hit1, hit3, hit10, n), as ReasoningPredictor::evaluate
     miner.eval_ranks(triples); miner.scores(triples)   # the (num_g, num_ge) pairs / the val rows behind it
 
-    python -m rnnlogic_amd.miner -data-path D -output-file F -max-length 3 ...   # main.cpp's flags
+    python -m rnnlogic_amd.miner -data-path D -output-file F -max-length 3 ...   # main.cpp's flags (-max-length 1..5)
     python -m rnnlogic_amd.miner -data-path D -output-file F ... -evaluate both  # + one metrics line per split
     python -m rnnlogic_amd.miner -data-path D -rule-file F -evaluate test        # evaluate a rule file, no mining
 
 The pool equals the reference's for the same train graph: every relation
 path of length <= max_length from h to t of a train triple (h, r, t), the
 triple's own edge removed, as the rule r <- path; r <- r dropped; per head in
-std::set<Rule> order (length, then body).  max_length <= 3.
+std::set<Rule> order (length, then body).  Bodies of up to three relations by
+default; RuleMiner(graph, max_body=4 or 5) takes longer ones in search,
+set_logic_rules, read_rules and mine (rnnl_rule_search_long: lengths 4 and 5
+as the exact join of the forward paths from h with the length-2 suffixes into
+t; at most 4,096 relations at length 4 and 1,024 at 5, the 64-bit key).  There
+a triple with h == t gives the reference's one rule without a body;
+search(max_length <= 3) walks on from such a triple, as it always did.
 
 learn / h_score compute what the reference computes with one thread: a pure
 function of the triple order (its multi-threaded run races on the weights and
@@ -73,10 +79,62 @@ def flatten_weights(rule_off, rel2weights):
     return flat
 
 
-def read_rule_file(file_name, n_relations):
+MAX_BODY = 5  # the longest body the native miner holds (RULE_STRIDE, csrc/internal.h)
+
+
+def _check_max_body(max_body):
+    if max_body not in (3, 4, 5):
+        raise ValueError("max_body must be 3, 4 or 5 (got %r)" % (max_body,))
+    return int(max_body)
+
+
+def _too_long(what, max_body):
+    if max_body < MAX_BODY:
+        return "%s: rule bodies have at most %d relations (raise the limit with max_body=, up to %d)" % (
+            what, max_body, MAX_BODY)
+    return "%s: rule bodies have at most %d relations" % (what, max_body)
+
+
+def long_key_bits(n_relations, max_length):
+    """Bits per relation of a long rule key (rnnl_rule_key_bits): max(1,
+    ceil(log2 R)); raises the native RNNL_ERR_INVALID, naming the bound, unless
+    3 + (max_length + 1) * bits <= 64."""
+    bits = ctypes.c_int32()
+    _native.call("rnnl_rule_key_bits", int(n_relations), int(max_length), ctypes.byref(bits))
+    return bits.value
+
+
+def encode_long(rules, n_relations, max_length):
+    """[(head, body)] -> long rule keys (numpy uint64): head | len (3 bits) |
+    b1 .. b_max_length, `long_key_bits` per relation, bodies left-aligned."""
+    bits = long_key_bits(n_relations, max_length)
+    keys = np.zeros(len(rules), dtype=np.uint64)
+    for i, (hd, body) in enumerate(rules):
+        if len(body) > max_length:
+            raise ValueError("encode_long: a body of %d relations in keys of max_length %d" % (len(body), max_length))
+        k = ((int(hd) << 3) | len(body)) << (max_length * bits)
+        for j, b in enumerate(body):
+            k |= int(b) << ((max_length - 1 - j) * bits)
+        keys[i] = k
+    return keys
+
+
+def unpack_long(keys, n_relations, max_length):
+    """long rule keys -> (head int64, length int32, body int32 (n, max_length)), in the order given."""
+    bits = long_key_bits(n_relations, max_length)
+    keys = np.asarray(keys, dtype=np.uint64)
+    m = np.uint64((1 << bits) - 1)
+    top = keys >> np.uint64(max_length * bits)
+    body = np.stack([(keys >> np.uint64((max_length - 1 - j) * bits)) & m for j in range(max_length)], 1)
+    return (top >> np.uint64(3)).astype(np.int64), (top & np.uint64(7)).astype(np.int32), body.astype(np.int32)
+
+
+def read_rule_file(file_name, n_relations, max_body=3):
     """A rule file of 'head body... x' lines (out_rules / mined_rules.txt) ->
     (rel2rules, rel2weights) in file order per head.  A last token that is not
-    an integer is x, the weight; a line of integers alone has weight 0."""
+    an integer is x, the weight; a line of integers alone has weight 0.  A body
+    of more than max_body (3..5) relations is refused."""
+    max_body = _check_max_body(max_body)
     rel2rules = [[] for _ in range(n_relations)]
     rel2weights = [[] for _ in range(n_relations)]
     with open(file_name) as fi:
@@ -101,8 +159,8 @@ def read_rule_file(file_name, n_relations):
                 raise ValueError("%s:%d: no head relation" % (file_name, no))
             if any(v < 0 or v >= n_relations for v in ids):
                 raise ValueError("%s:%d: relation id out of range [0, %d)" % (file_name, no, n_relations))
-            if len(ids) > 4:
-                raise ValueError("%s:%d: rule bodies have at most 3 relations" % (file_name, no))
+            if len(ids) > max_body + 1:
+                raise ValueError(_too_long("%s:%d" % (file_name, no), max_body))
             if not math.isfinite(x):
                 raise ValueError("%s:%d: the weight is not finite" % (file_name, no))
             rel2rules[ids[0]].append((ids[0], tuple(ids[1:])))
@@ -147,9 +205,12 @@ def metrics_line(name, m):
 
 
 class RuleMiner(object):
+    max_body = 3  # the longest rule body search / set_logic_rules / read_rules / mine take; 3..5 per miner
 
-    def __init__(self, graph, device=None):
+    def __init__(self, graph, device=None, max_body=3):
         self.graph = graph
+        self.max_body = _check_max_body(max_body)
+        self.suffix_cap = 0           # long search: length-2 suffixes of a tail sorted in LDS (0: the most, 2,048)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         hrt = np.ascontiguousarray(np.asarray(graph.train_facts, dtype=np.int32).reshape(-1, 3))
         self._handle = ctypes.c_void_p()
@@ -179,9 +240,14 @@ class RuleMiner(object):
                 pass
 
     @staticmethod
-    def decode(keys):
-        """rule keys (head<<47 | len<<45 | b1<<30 | b2<<15 | b3) -> [(head, body)] in key order."""
+    def decode(keys, n_relations=None, max_length=None):
+        """rule keys (head<<47 | len<<45 | b1<<30 | b2<<15 | b3) -> [(head, body)] in key order.
+        With n_relations and max_length (4 or 5): the long keys of search_keys(max_length)."""
         keys = np.sort(np.asarray(keys, dtype=np.uint64))
+        if max_length is not None and max_length > 3:
+            head, ln, b = unpack_long(keys, n_relations, max_length)
+            b = b.tolist()
+            return [(hd, tuple(b[i][:n])) for i, (hd, n) in enumerate(zip(head.tolist(), ln.tolist()))]
         m = np.uint64(0x7FFF)
         head = (keys >> np.uint64(47)).astype(np.int64)
         ln = ((keys >> np.uint64(45)) & np.uint64(3)).astype(np.int64)
@@ -190,15 +256,30 @@ class RuleMiner(object):
 
     @torch.no_grad()
     def search_keys(self, max_length):
-        """Device search; returns the distinct rule keys (numpy uint64, unsorted)."""
+        """Device search; returns the distinct rule keys (numpy uint64, unsorted):
+        the keys of decode() for max_length <= 3, the long keys (unpack_long)
+        for 4 and 5."""
+        if max_length > self.max_body:
+            raise ValueError(_too_long("search(%d)" % max_length, self.max_body))
+        long_form = max_length > 3
+        if long_form:
+            long_key_bits(self.graph.relation_size, max_length)  # RNNL_ERR_INVALID before anything is allocated
         stream = torch.cuda.current_stream(self.device).cuda_stream
         counters = torch.zeros(4, dtype=torch.int64, device=self.device)
         while True:
             cap = 1 << self.table_bits
+            if long_form and 16 * cap > self.budget_bytes:
+                raise RuntimeError("rule search: the rule set needs a table of 2 x %d bytes, past budget_bytes = %d"
+                                   % (8 * cap, self.budget_bytes))
             table = torch.empty(cap, dtype=torch.int64, device=self.device)
             out = torch.empty(cap, dtype=torch.int64, device=self.device)
-            _native.call("rnnl_rule_search", self._handle, int(max_length), table.data_ptr(), cap, out.data_ptr(),
-                         cap, counters.data_ptr(), stream)
+            if long_form:
+                with torch.cuda.device(self.device):
+                    _native.call("rnnl_rule_search_long", self._handle, int(max_length), int(self.suffix_cap),
+                                 table.data_ptr(), cap, out.data_ptr(), cap, counters.data_ptr(), stream)
+            else:
+                _native.call("rnnl_rule_search", self._handle, int(max_length), table.data_ptr(), cap, out.data_ptr(),
+                             cap, counters.data_ptr(), stream)
             c = counters.cpu().tolist()
             if c[1] == 0 and c[2] <= cap // 2:
                 return out[:c[2]].cpu().numpy().view(np.uint64)
@@ -209,13 +290,20 @@ class RuleMiner(object):
     def search(self, max_length):
         """RuleMiner::search over all train triples (portion 1)."""
         keys = np.sort(self.search_keys(max_length))
+        self._searched = max_length
+        if max_length > 3:
+            self.rules = self.decode(keys, self.graph.relation_size, max_length)
+            head, ln, body = unpack_long(keys, self.graph.relation_size, max_length)
+            wide = np.zeros((len(keys), MAX_BODY), dtype=np.int32)
+            wide[:, :max_length] = body
+            self._pool_arrays = (head, ln, wide)
+            return self.rules
         self.rules = self.decode(keys)
         m = np.uint64(0x7FFF)
         self._pool_arrays = ((keys >> np.uint64(47)).astype(np.int64),  # head, length, body of self.rules
                              ((keys >> np.uint64(45)) & np.uint64(3)).astype(np.int32),
                              np.stack([(keys >> np.uint64(30)) & m, (keys >> np.uint64(15)) & m, keys & m],
                                       1).astype(np.int32))
-        self._searched = max_length
         return self.rules
 
     def get_logic_rules(self):
@@ -229,8 +317,10 @@ class RuleMiner(object):
     def set_logic_rules(self, rel2rules, priors=None):
         """ReasoningPredictor::set_logic_rules: rel2rules[r] = [(head, body)]
         are relation r's rules, in list order; weights, Adam state and H are
-        cleared.  priors[r][k] (default 0) enters h_score with prior_weight."""
+        cleared.  priors[r][k] (default 0) enters h_score with prior_weight.
+        Bodies hold at most max_body relations."""
         R = self.graph.relation_size
+        width = 3 if self.max_body == 3 else MAX_BODY
         if len(rel2rules) != R:
             raise ValueError("set_logic_rules: one rule list per relation expected")
         off, ln, body, pr = [0], [], [], []
@@ -238,22 +328,23 @@ class RuleMiner(object):
             for k, (hd, b) in enumerate(rules):
                 if int(hd) != r:
                     raise ValueError("set_logic_rules: rule with head %d in the list of relation %d" % (hd, r))
-                if len(b) > 3:
-                    raise ValueError("set_logic_rules: rule bodies have at most 3 relations")
+                if len(b) > self.max_body:
+                    raise ValueError(_too_long("set_logic_rules", self.max_body))
                 ln.append(len(b))
-                body.append([int(x) for x in b] + [0] * (3 - len(b)))
+                body.append([int(x) for x in b] + [0] * (width - len(b)))
                 pr.append(float(priors[r][k]) if priors is not None else 0.0)
             off.append(len(ln))
-        self._set_rule_arrays(off, ln, np.asarray(body, dtype=np.int32).reshape(-1, 3), pr)
+        self._set_rule_arrays(off, ln, np.asarray(body, dtype=np.int32).reshape(-1, width), pr)
 
     def _set_rule_arrays(self, off, ln, body, prior):
         self._rule_off = np.ascontiguousarray(off, dtype=np.int32)
         ln = np.ascontiguousarray(ln, dtype=np.int32)
         body = np.ascontiguousarray(body, dtype=np.int32)
         pr = np.ascontiguousarray(prior, dtype=np.float64)
+        entry = "rnnl_miner_set_rules" if body.shape[1] == 3 else "rnnl_miner_set_rules_long"  # n x 3 / n x 5
         with torch.cuda.device(self.device):
-            _native.call("rnnl_miner_set_rules", self._handle, self._rule_off.ctypes.data, ln.ctypes.data,
-                         body.ctypes.data, pr.ctypes.data)
+            _native.call(entry, self._handle, self._rule_off.ctypes.data, ln.ctypes.data, body.ctypes.data,
+                         pr.ctypes.data)
         self._grounded = None
 
     def _use_order(self, order, portion):
@@ -383,7 +474,7 @@ class RuleMiner(object):
         """Sets the rules of a 'head body... x' file (out_rules /
         mined_rules.txt), in file order per head, with x as the weight.
         Returns the number of rules read."""
-        rel2rules, rel2weights = read_rule_file(file_name, self.graph.relation_size)
+        rel2rules, rel2weights = read_rule_file(file_name, self.graph.relation_size, self.max_body)
         self.set_logic_rules(rel2rules)
         self.set_weights(rel2weights)
         return sum(len(x) for x in rel2rules)
@@ -453,6 +544,8 @@ class RuleMiner(object):
         of the train triples) and selections[it][r] (pool indices) replace the
         seeded draws, so a reference run can be replayed.  Returns the rules
         out_rules would write: [(head, body, H)]."""
+        if max_length > self.max_body:
+            raise ValueError(_too_long("mine(max_length=%d)" % max_length, self.max_body))
         if not self.rules or self._searched != max_length:
             self.search(max_length)
         pool = self.get_logic_rules()
@@ -538,7 +631,11 @@ def main(argv=None):
         ap.error("the following arguments are required: -output-file")
     if a.rule_file is not None and (a.output_file is not None or a.evaluate is None):
         ap.error("-rule-file evaluates a rule file: give -evaluate, and no -output-file")
-    miner = RuleMiner(KnowledgeGraph(a.data_path))
+    if a.rule_file is None and not 1 <= a.max_length <= MAX_BODY:
+        ap.error("-max-length must be 1..%d" % MAX_BODY)
+    # mining: bodies as long as asked for; a rule file: as long as the miner holds
+    miner = RuleMiner(KnowledgeGraph(a.data_path),
+                      max_body=MAX_BODY if a.rule_file is not None else max(3, a.max_length))
     if a.output_file is not None:
         miner.mine(a.max_length, a.iterations, a.top_n, a.top_k, a.lr, a.wd, a.temp, a.top_n_out, seed=a.seed)
         print("#Rules written: %d" % miner.out_rules(a.output_file, a.top_n_out))
