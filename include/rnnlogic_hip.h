@@ -707,6 +707,40 @@ int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const i
                         const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t *ranks,
                         double *val, uint64_t *counters, void *stream);
 
+/* ------------------------------------- support and confidence of rules --
+ * The exact counts behind standard and PCA confidence, on the handle's train
+ * graph as given: no inverses, and — unlike search, learn and evaluate — no
+ * edge removed.  With D_b(x) the entities reachable from x along the body b
+ * (D(x) = {x} for the empty body) and T_r(x) the distinct tails of (x, r):
+ *   body(b) = sum_x |D_b(x)|, support(r, b) = sum_x |D_b(x) & T_r(x)|,
+ *   pca_body(r, b) = sum over x with T_r(x) not empty of |D_b(x)|.
+ *
+ *   rnnl_miner_rule_stats: the rules arrive grouped by body, as host arrays:
+ *     body_len (n_bodies, 0..5), body_rel (n_bodies x 5), and per body the
+ *     heads asked for as a CSR head_off (n_bodies + 1, head_off[0] = 0, not
+ *     decreasing) / head_rel (head_off[n_bodies] relations, ascending and
+ *     distinct within a body).  All of it is checked before any device call
+ *     (RNNL_ERR_INVALID).  out (device, n_bodies + 2 * slots uint64, zeroed
+ *     here) receives body per body, then support per slot, then pca_body per
+ *     slot.  work (device, work_bytes >= what rnnl_miner_rule_stats_scratch
+ *     returns for the same n_bodies, slots and max_blocks) holds the device
+ *     copy of the arrays and, for graphs of more than 1,024 entities, the
+ *     walk's stamps and frontier lists; it is the caller's, so a call shares
+ *     nothing with an evaluation in flight.  max_blocks > 0 bounds the grid
+ *     (0: the default).  first_stamp is the visited stamp the walk starts
+ *     from (0 by default; the stamps wrap past 2^32 - 1, any value gives the
+ *     same counts).  counters (device, 4 x uint64, zeroed here): [3] != 0:
+ *     internal; [1], [2] stay 0 (nothing can overflow, the arguments are
+ *     checked on the host).  Integer atomics only: exact and bitwise
+ *     repeatable.  The handle's rule lists, weights, Adam state, H and val are
+ *     neither read nor changed.  Asynchronous on `stream`; the host arrays
+ *     may be released on return. */
+int rnnl_miner_rule_stats_scratch(rnnl_miner m, int64_t n_bodies, int64_t n_slots, int32_t max_blocks,
+                                  size_t *bytes);
+int rnnl_miner_rule_stats(rnnl_miner m, int64_t n_bodies, const int32_t *body_len, const int32_t *body_rel,
+                          const int32_t *head_off, const int32_t *head_rel, int32_t max_blocks, uint32_t first_stamp,
+                          void *work, size_t work_bytes, uint64_t *out, uint64_t *counters, void *stream);
+
 /* ------------------------------------------------------- training loss --
  * TrainerPredictor.train's loss (reference src/trainer.py:84-90) for a model
  * whose mask is all True (bias / RotatE features): with

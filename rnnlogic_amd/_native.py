@@ -117,6 +117,9 @@ SIGNATURES = [
     ("rnnl_miner_read", ctypes.c_int, [_P, _P, _P, _P]),
     ("rnnl_miner_set_weights", ctypes.c_int, [_P, _P, _P]),
     ("rnnl_miner_evaluate", ctypes.c_int, [_P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    ("rnnl_miner_rule_stats_scratch", ctypes.c_int, [_P, _I64, _I64, _I32, _P]),
+    ("rnnl_miner_rule_stats", ctypes.c_int,
+     [_P, _I64, _P, _P, _P, _P, _I32, ctypes.c_uint32, _P, ctypes.c_size_t, _P, _P, _P]),
     ("rnnl_rotate_score", ctypes.c_int,
      [_P, _P, _P, _I32, _F32, _P, _P, _I32, _I32, _P, _I32, _I32, _P, ctypes.c_size_t, _P]),
     ("rnnl_rotate_score_pieces", ctypes.c_int,

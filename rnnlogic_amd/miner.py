@@ -19,6 +19,13 @@ running mean (RuleGenerator::update) and the rule file (out_rules)
     miner.evaluate("test")              # dict(mr, mrr, hit1, hit3, hit10, n), as ReasoningPredictor::evaluate
     miner.eval_ranks(triples); miner.scores(triples)   # the (num_g, num_ge) pairs / the val rows behind it
 
+    miner.rule_stats()                  # dict(support, body, pca_body): int64 per rule of the current lists (or of
+    miner.pool_stats()                  # rel2rules given) / of the searched pool, in get_logic_rules() order
+    miner.head_pairs(); miner.confidence("pca" | "std" | "head_coverage", pc=0.0)
+    miner.mine(..., prior="pca", prior_weight=0.5)     # that confidence as the prior H_score weighs
+    miner.out_rules(F, top_n_out, min_support=1, min_confidence=0.1, confidence="pca", pc=0.0)
+    miner.out_rule_stats(S, top_n_out)  # "head body... H support body pca_body std pca" of the rules out_rules writes
+
     python -m rnnlogic_amd.miner -data-path D -output-file F -max-length 3 ...   # main.cpp's flags (-max-length 1..5)
     python -m rnnlogic_amd.miner -data-path D -output-file F ... -evaluate both  # + one metrics line per split
     python -m rnnlogic_amd.miner -data-path D -rule-file F -evaluate test        # evaluate a rule file, no mining
@@ -204,6 +211,70 @@ def metrics_line(name, m):
                                                                   m["hit10"])
 
 
+def group_rules(head, ln, body, n_relations):
+    """Rules as arrays (head (n,), length (n,), body (n, w <= MAX_BODY)) ->
+    what rnnl_miner_rule_stats takes and the way back: (body_len (nb,) int32,
+    body_rel (nb, MAX_BODY) int32, head_off (nb + 1,) int32, head_rel int32,
+    body_of (n,), slot_of (n,)).  Every distinct body once, per body its
+    distinct heads ascending; rule i reads body count body_of[i] and
+    (support, pca_body) slot slot_of[i], so a (head, body) listed twice reads
+    the same slot twice."""
+    head = np.asarray(head, dtype=np.int64).reshape(-1)
+    ln = np.asarray(ln, dtype=np.int64).reshape(-1)
+    n, R = len(head), max(int(n_relations), 1)
+    wide = np.zeros((n, MAX_BODY), dtype=np.int64)
+    body = np.asarray(body, dtype=np.int64).reshape(n, -1)
+    wide[:, :body.shape[1]] = body
+    wide[np.arange(MAX_BODY)[None, :] >= ln[:, None]] = 0  # whatever lies past a body's end does not tell bodies apart
+    if (MAX_BODY + 1) * R ** MAX_BODY < 2 ** 62:
+        key = ln.copy()
+        for j in range(MAX_BODY):
+            key = key * R + wide[:, j]
+        ukey, first, body_of = np.unique(key, return_index=True, return_inverse=True)
+        ub = np.concatenate([ln[first, None], wide[first]], 1)
+    else:
+        ub, body_of = np.unique(np.concatenate([ln[:, None], wide], 1), axis=0, return_inverse=True)
+    body_of = body_of.reshape(-1)
+    nb = len(ub)
+    uslot, slot_of = np.unique(body_of * R + head, return_inverse=True)
+    head_off = np.searchsorted(uslot // R, np.arange(nb + 1)).astype(np.int32)
+    return (np.ascontiguousarray(ub[:, 0], dtype=np.int32), np.ascontiguousarray(ub[:, 1:], dtype=np.int32), head_off,
+            np.ascontiguousarray(uslot % R, dtype=np.int32), body_of, slot_of.reshape(-1))
+
+
+def confidence_of(support, denominator, pc=0.0):
+    """support / (denominator + pc) in fp64, 0 / 0 = 0.0 (pc >= 0: AnyBURL's pessimistic constant)."""
+    if not pc >= 0.0:
+        raise ValueError("pc must be >= 0 (got %r)" % (pc,))
+    sup = np.asarray(support, dtype=np.float64)
+    den = np.asarray(denominator, dtype=np.float64) + float(pc)
+    out = np.zeros(sup.shape, dtype=np.float64)
+    np.divide(sup, den, out=out, where=den > 0.0)
+    return out
+
+
+def confidences(kind, support, body, pca_body, head_pairs, pc=0.0):
+    """'std': support / (body + pc); 'pca': support / (pca_body + pc);
+    'head_coverage': support / head_pairs (of the rule's head)."""
+    if kind == "std":
+        return confidence_of(support, body, pc)
+    if kind == "pca":
+        return confidence_of(support, pca_body, pc)
+    if kind == "head_coverage":
+        return confidence_of(support, head_pairs, 0.0)
+    raise ValueError("confidence: kind must be 'std', 'pca' or 'head_coverage' (got %r)" % (kind,))
+
+
+def keep_rules(support, conf, min_support=0, min_confidence=0.0):
+    """The filter of best_rules / out_rules: True where a rule stays."""
+    return (np.asarray(support) >= min_support) & (np.asarray(conf) >= min_confidence)
+
+
+def stats_line(head, body, x, support, body_size, pca_body, std, pca):
+    return "%d%s %.16f %d %d %d %.16f %.16f\n" % (head, "".join(" %d" % b for b in body), x, support, body_size,
+                                                  pca_body, std, pca)
+
+
 class RuleMiner(object):
     max_body = 3  # the longest rule body search / set_logic_rules / read_rules / mine take; 3..5 per miner
 
@@ -230,6 +301,10 @@ class RuleMiner(object):
         self.chunk_triples = None     # triples per grounding chunk; None: as many as budget_bytes allows
         self.budget_bytes = 1 << 30   # device memory for one chunk's (triple, rule, destination, count) entries
         self._known = None            # known tails over train + valid + test (eval_ranks), built once
+        self._rule_len = np.zeros(0, dtype=np.int32)       # the current rule lists, as _set_rule_arrays got them
+        self._rule_body = np.zeros((0, 3), dtype=np.int32)
+        self._pool_stats = None       # pool_stats() of the searched pool, until the next search
+        self._head_pairs = None
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -291,6 +366,7 @@ class RuleMiner(object):
         """RuleMiner::search over all train triples (portion 1)."""
         keys = np.sort(self.search_keys(max_length))
         self._searched = max_length
+        self._pool_stats = None
         if max_length > 3:
             self.rules = self.decode(keys, self.graph.relation_size, max_length)
             head, ln, body = unpack_long(keys, self.graph.relation_size, max_length)
@@ -341,6 +417,7 @@ class RuleMiner(object):
         ln = np.ascontiguousarray(ln, dtype=np.int32)
         body = np.ascontiguousarray(body, dtype=np.int32)
         pr = np.ascontiguousarray(prior, dtype=np.float64)
+        self._rule_len, self._rule_body = ln, body
         entry = "rnnl_miner_set_rules" if body.shape[1] == 3 else "rnnl_miner_set_rules_long"  # n x 3 / n x 5
         with torch.cuda.device(self.device):
             _native.call(entry, self._handle, self._rule_off.ctypes.data, ln.ctypes.data, body.ctypes.data,
@@ -459,6 +536,117 @@ class RuleMiner(object):
         """Per relation, the H score of each rule of its list (float64)."""
         return self._read(1)
 
+    # ------------------------------------------- support and confidence
+    @torch.no_grad()
+    def _stats_arrays(self, head, ln, body, max_blocks=0, first_stamp=0):
+        """(support, body, pca_body), int64 per rule, of rules given as arrays
+        (rnnl_miner_rule_stats): each distinct body is walked once per source
+        entity whatever the number of heads and copies it is listed with."""
+        if len(head) == 0:
+            return tuple(np.zeros(0, dtype=np.int64) for _ in range(3))
+        return self._stats_grouped(group_rules(head, ln, body, self.graph.relation_size), max_blocks, first_stamp)
+
+    @torch.no_grad()
+    def _stats_grouped(self, grouped, max_blocks=0, first_stamp=0):
+        """_stats_arrays of rules that group_rules has grouped already."""
+        body_len, body_rel, head_off, head_rel, body_of, slot_of = grouped
+        nb, ns = len(body_len), len(head_rel)
+        nbytes = ctypes.c_size_t()
+        _native.call("rnnl_miner_rule_stats_scratch", self._handle, nb, ns, int(max_blocks), ctypes.byref(nbytes))
+        with torch.cuda.device(self.device):
+            work = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            out = torch.empty(nb + 2 * ns, dtype=torch.int64, device=self.device)
+            counters = torch.zeros(4, dtype=torch.int64, device=self.device)  # not the evaluation's
+            _native.call("rnnl_miner_rule_stats", self._handle, nb, body_len.ctypes.data, body_rel.ctypes.data,
+                         head_off.ctypes.data, head_rel.ctypes.data, int(max_blocks), int(first_stamp),
+                         work.data_ptr(), nbytes.value, out.data_ptr(), counters.data_ptr(),
+                         torch.cuda.current_stream(self.device).cuda_stream)
+            flat = out.cpu().numpy()
+            c = counters.cpu().tolist()
+        if c[1] or c[2] or c[3]:
+            raise _native.NativeError(_native.RNNL_ERR_INTERNAL, "rule statistics failed (flags %r)" % (c[1:],))
+        return flat[nb:nb + ns][slot_of], flat[:nb][body_of], flat[nb + ns:][slot_of]
+
+    def _listed(self, rel2rules):
+        """(head, length, body, offsets) of rel2rules, or of the current lists."""
+        R = self.graph.relation_size
+        if rel2rules is None:
+            off = self._rule_off.astype(np.int64)
+            return np.repeat(np.arange(R), np.diff(off)), self._rule_len, self._rule_body, off
+        if len(rel2rules) != R:
+            raise ValueError("rule_stats: one rule list per relation expected")
+        head, ln, body = [], [], []
+        for r, rules in enumerate(rel2rules):
+            for hd, b in rules:
+                if int(hd) != r:
+                    raise ValueError("rule_stats: rule with head %d in the list of relation %d" % (hd, r))
+                if len(b) > MAX_BODY:
+                    raise ValueError(_too_long("rule_stats", MAX_BODY))
+                if any(int(x) < 0 or int(x) >= R for x in b):
+                    raise ValueError("rule_stats: body relation out of range [0, %d)" % R)
+                head.append(r)
+                ln.append(len(b))
+                body.append([int(x) for x in b] + [0] * (MAX_BODY - len(b)))
+        off = np.concatenate([[0], np.cumsum([len(x) for x in rel2rules])]).astype(np.int64)
+        return (np.asarray(head, dtype=np.int64), np.asarray(ln, dtype=np.int32),
+                np.asarray(body, dtype=np.int32).reshape(-1, MAX_BODY), off)
+
+    @staticmethod
+    def _per_relation(flat, off):
+        return [flat[a:b] for a, b in zip(off[:-1], off[1:])]
+
+    def rule_stats(self, rel2rules=None, max_blocks=0):
+        """dict(support, body, pca_body): per relation an int64 array parallel
+        to its rule list — rel2rules[r] = [(head, body)], or the current lists
+        of set_logic_rules / read_rules.  Exact counts on the whole train
+        graph, no edge removed (unlike search, learn and evaluate): support =
+        the known (h, t) pairs of the head the body reaches, body = all pairs
+        the body reaches, pca_body = those whose h has some known tail.  The
+        handle's rules, weights and H are not touched.  max_blocks bounds the
+        kernel's grid (0: the default)."""
+        head, ln, body, off = self._listed(rel2rules)
+        sup, bod, pca = self._stats_arrays(head, ln, body, max_blocks)
+        return dict(support=self._per_relation(sup, off), body=self._per_relation(bod, off),
+                    pca_body=self._per_relation(pca, off))
+
+    def head_pairs(self):
+        """int64 per relation: its distinct (h, t) pairs in train."""
+        if self._head_pairs is None:
+            R = self.graph.relation_size
+            rel = np.unique(self._hrt.reshape(-1, 3), axis=0)[:, 1] if len(self._hrt) else np.zeros(0, np.int64)
+            self._head_pairs = np.bincount(rel, minlength=R).astype(np.int64)
+        return self._head_pairs
+
+    def confidence(self, kind="pca", pc=0.0, rel2rules=None):
+        """Per relation a float64 array parallel to its rule list: 'std' =
+        support / (body + pc), 'pca' = support / (pca_body + pc),
+        'head_coverage' = support / head_pairs; 0 / 0 is 0.0."""
+        confidences(kind, [], [], [], [], pc)  # a bad kind or pc before any device work
+        st = self.rule_stats(rel2rules)
+        hp = self.head_pairs()
+        return [confidences(kind, s, b, p, hp[r], pc)
+                for r, (s, b, p) in enumerate(zip(st["support"], st["body"], st["pca_body"]))]
+
+    def _pool_flat(self):
+        if self._searched is None:
+            raise RuntimeError("RuleMiner.pool_stats: call search() or mine() first")
+        if self._pool_stats is None:
+            p_head, p_len, p_body = self._pool_arrays  # no Python tuples on the way
+            self._pool_stats = self._stats_arrays(p_head, p_len, p_body)
+        return self._pool_stats
+
+    def pool_stats(self):
+        """rule_stats of the searched pool, per relation in get_logic_rules()
+        order; computed once per search."""
+        sup, bod, pca = self._pool_flat()
+        off = np.searchsorted(self._pool_arrays[0], np.arange(self.graph.relation_size + 1))
+        return dict(support=self._per_relation(sup, off), body=self._per_relation(bod, off),
+                    pca_body=self._per_relation(pca, off))
+
+    def _pool_confidence(self, kind, pc):
+        sup, bod, pca = self._pool_flat()
+        return confidences(kind, sup, bod, pca, self.head_pairs()[self._pool_arrays[0]], pc)
+
     # ------------------------------------------------------------ evaluation
     def set_weights(self, rel2weights):
         """rel2weights[r][k] (float64) becomes the weight of rule k of relation
@@ -537,15 +725,20 @@ class RuleMiner(object):
         return expectation_metrics(self.eval_ranks(triples, filtered), self.graph.entity_size)
 
     def mine(self, max_length, iterations, top_n, top_k, lr, wd, temp, top_n_out=0, seed=0, orders=None,
-             selections=None, portion=1.0):
+             selections=None, portion=1.0, prior=None, prior_weight=0.0, pc=0.0):
         """The reference miner's main loop (miner/main.cpp:27-49): search, then
         per iteration a rule subset per relation (top_n, 0 = all), learn,
         H_score and the pool's running mean of H.  orders[it] (a permutation
         of the train triples) and selections[it][r] (pool indices) replace the
-        seeded draws, so a reference run can be replayed.  Returns the rules
+        seeded draws, so a reference run can be replayed.  prior ('std' or
+        'pca', with pc) makes that confidence of each selected rule its prior,
+        which enters H_score as prior * prior_weight (the reference's slot;
+        None: priors of 0, as the reference's miner).  Returns the rules
         out_rules would write: [(head, body, H)]."""
         if max_length > self.max_body:
             raise ValueError(_too_long("mine(max_length=%d)" % max_length, self.max_body))
+        if prior not in (None, "std", "pca"):
+            raise ValueError("mine: prior must be None, 'std' or 'pca' (got %r)" % (prior,))
         if not self.rules or self._searched != max_length:
             self.search(max_length)
         pool = self.get_logic_rules()
@@ -555,6 +748,7 @@ class RuleMiner(object):
         cn = [np.zeros(len(p), dtype=np.float64) for p in pool]
         p_head, p_len, p_body = self._pool_arrays  # the pool in search order: per head, then by key
         pool_off = np.searchsorted(p_head, np.arange(R + 1))
+        pool_prior = self._pool_confidence(prior, pc) if prior is not None else None
         rng = np.random.default_rng(seed)
         for it in range(iterations):
             if selections is not None:
@@ -565,35 +759,91 @@ class RuleMiner(object):
                                          dtype=np.int32)
             take = np.concatenate([pool_off[r] + sel[r] for r in range(R)]) if R else np.zeros(0, np.int64)
             off = np.concatenate([[0], np.cumsum([len(x) for x in sel])])
-            self._set_rule_arrays(off, p_len[take], p_body[take], np.zeros(len(take)))  # = set_logic_rules(subset)
+            self._set_rule_arrays(off, p_len[take], p_body[take],  # = set_logic_rules(subset, priors)
+                                  pool_prior[take] if pool_prior is not None else np.zeros(len(take)))
             self.learn(lr, wd, temp, False, portion, order)
-            self.h_score(top_k, 1.0, 0.0, portion, self._order)
+            self.h_score(top_k, 1.0, float(prior_weight), portion, self._order)
             for r, H in enumerate(self.H()):  # RuleGenerator::update
                 self.pool_H[r][sel[r]] = (self.pool_H[r][sel[r]] * cn[r][sel[r]] + H) / (cn[r][sel[r]] + 1)
                 cn[r][sel[r]] += 1
         self._grounded = None
         return self.best_rules(top_n_out)
 
-    def best_rules(self, top_n_out=0):
-        """Per relation the pool's rules by H descending, then pool order; the
-        first top_n_out (0 = all): [(head, body, H)]."""
+    def _best(self, top_n_out, min_support, min_confidence, confidence, pc, want_stats):
+        """Per relation the pool indices best_rules keeps, in its order, and the
+        pool's statistics (None unless a bound or want_stats asks for them)."""
         if self.pool is None:
             raise RuntimeError("RuleMiner.best_rules / out_rules: call mine() first")
+        filtering = min_support > 0 or min_confidence > 0.0
+        st = conf = None
+        if filtering or want_stats:
+            st = self.pool_stats()
+            hp = self.head_pairs()
+            conf = {kind: [confidences(kind, st["support"][r], st["body"][r], st["pca_body"][r], hp[r], pc)
+                           for r in range(len(self.pool))]
+                    for kind in set(["std", "pca", confidence])}
+            if any(len(a) != len(b) for a, b in zip(st["support"], self.pool)):
+                raise RuntimeError("RuleMiner.best_rules: the pool was searched again since mine()")
+        picks = []
+        for r in range(len(self.pool)):
+            idx = np.argsort(-self.pool_H[r], kind="stable")
+            if filtering:  # rules below either bound leave before top_n_out counts
+                idx = idx[keep_rules(st["support"][r], conf[confidence][r], min_support, min_confidence)[idx]]
+            picks.append(idx[:top_n_out if top_n_out else None])
+        return picks, st, conf
+
+    def best_rules(self, top_n_out=0, min_support=0, min_confidence=0.0, confidence="pca", pc=0.0):
+        """Per relation the pool's rules by H descending, then pool order; the
+        first top_n_out (0 = all) of those with support >= min_support and
+        confidence ('std', 'pca' or 'head_coverage', with pc) >=
+        min_confidence: [(head, body, H)]."""
+        picks, _, _ = self._best(top_n_out, min_support, min_confidence, confidence, pc, False)
         out = []
         for r, rules in enumerate(self.pool):
-            idx = np.argsort(-self.pool_H[r], kind="stable")
-            for k in idx[:top_n_out if top_n_out else None]:
+            for k in picks[r]:
                 out.append((rules[k][0], rules[k][1], float(self.pool_H[r][k])))
         return out
 
-    def out_rules(self, file_name, top_n_out=0):
+    def out_rules(self, file_name, top_n_out=0, min_support=0, min_confidence=0.0, confidence="pca", pc=0.0):
         """RuleGenerator::out_rules (rnnlogic.cpp:1904-1935): 'head body... H'
-        with H as %.16f — the mined_rules.txt of the reference pipeline."""
-        rules = self.best_rules(top_n_out)
+        with H as %.16f — the mined_rules.txt of the reference pipeline.  The
+        bounds are best_rules'."""
+        rules = self.best_rules(top_n_out, min_support, min_confidence, confidence, pc)
         with open(file_name, "w") as fo:
             for hd, body, H in rules:
                 fo.write("%d%s %.16f\n" % (hd, "".join(" %d" % x for x in body), H))
         return len(rules)
+
+    def out_rule_stats(self, file_name, top_n_out=0, min_support=0, min_confidence=0.0, confidence="pca", pc=0.0):
+        """The rules out_rules writes with the same arguments, one line each:
+        'head body... H support body pca_body std pca' (H and the two
+        confidences as %.16f)."""
+        picks, st, conf = self._best(top_n_out, min_support, min_confidence, confidence, pc, True)
+        n = 0
+        with open(file_name, "w") as fo:
+            for r, rules in enumerate(self.pool):
+                for k in picks[r]:
+                    fo.write(stats_line(rules[k][0], rules[k][1], float(self.pool_H[r][k]), st["support"][r][k],
+                                        st["body"][r][k], st["pca_body"][r][k], conf["std"][r][k],
+                                        conf["pca"][r][k]))
+                    n += 1
+        return n
+
+    def write_list_stats(self, file_name, pc=0.0):
+        """The current rule lists (set_logic_rules / read_rules) with their
+        weight and statistics, in list order: 'head body... weight support
+        body pca_body std pca'."""
+        st, hp = self.rule_stats(), self.head_pairs()
+        body, ln, n = self._rule_body.tolist(), self._rule_len.tolist(), 0
+        with open(file_name, "w") as fo:
+            for r, wt in enumerate(self.weights()):
+                s, b, p = st["support"][r], st["body"][r], st["pca_body"][r]
+                std, pca = confidences("std", s, b, p, hp[r], pc), confidences("pca", s, b, p, hp[r], pc)
+                for k in range(len(wt)):
+                    i = int(self._rule_off[r]) + k
+                    fo.write(stats_line(r, body[i][:ln[i]], float(wt[k]), s[k], b[k], p[k], std[k], pca[k]))
+                    n += 1
+        return n
 
     def save(self, file_name):
         """RuleMiner::save (rnnlogic.cpp:591-610): 'type head body... H wt prior'
@@ -626,21 +876,38 @@ def main(argv=None):
     ap.add_argument("-seed", dest="seed", type=int, default=0)
     ap.add_argument("-evaluate", dest="evaluate", choices=["valid", "test", "both"], default=None)
     ap.add_argument("-rule-file", dest="rule_file", default=None)
+    ap.add_argument("-stats-file", dest="stats_file", default=None)
+    ap.add_argument("-min-support", dest="min_support", type=int, default=0)
+    ap.add_argument("-min-conf", dest="min_conf", type=float, default=0.0)
+    ap.add_argument("-conf", dest="conf", choices=["std", "pca"], default="pca")
+    ap.add_argument("-pc", dest="pc", type=float, default=0.0)
+    ap.add_argument("-prior", dest="prior", choices=["std", "pca"], default=None)
+    ap.add_argument("-prior-weight", dest="prior_weight", type=float, default=0.0)
     a = ap.parse_args(argv)
     if a.output_file is None and a.rule_file is None:
         ap.error("the following arguments are required: -output-file")
-    if a.rule_file is not None and (a.output_file is not None or a.evaluate is None):
+    if a.rule_file is not None and (a.output_file is not None or (a.evaluate is None and a.stats_file is None)):
         ap.error("-rule-file evaluates a rule file: give -evaluate, and no -output-file")
     if a.rule_file is None and not 1 <= a.max_length <= MAX_BODY:
         ap.error("-max-length must be 1..%d" % MAX_BODY)
+    if a.pc < 0.0 or a.min_support < 0:
+        ap.error("-pc and -min-support must be >= 0")
+    if a.rule_file is not None and (a.min_support or a.min_conf or a.prior is not None or a.prior_weight):
+        ap.error("-min-support, -min-conf, -prior and -prior-weight belong to mining, not to -rule-file")
     # mining: bodies as long as asked for; a rule file: as long as the miner holds
     miner = RuleMiner(KnowledgeGraph(a.data_path),
                       max_body=MAX_BODY if a.rule_file is not None else max(3, a.max_length))
     if a.output_file is not None:
-        miner.mine(a.max_length, a.iterations, a.top_n, a.top_k, a.lr, a.wd, a.temp, a.top_n_out, seed=a.seed)
-        print("#Rules written: %d" % miner.out_rules(a.output_file, a.top_n_out))
-    else:  # evaluate a rule file: no search, no learn
+        miner.mine(a.max_length, a.iterations, a.top_n, a.top_k, a.lr, a.wd, a.temp, a.top_n_out, seed=a.seed,
+                   prior=a.prior, prior_weight=a.prior_weight, pc=a.pc)
+        bounds = (a.min_support, a.min_conf, a.conf, a.pc)
+        print("#Rules written: %d" % miner.out_rules(a.output_file, a.top_n_out, *bounds))
+        if a.stats_file is not None:  # the pool's counts: the weights evaluated below stay the last iteration's
+            miner.out_rule_stats(a.stats_file, a.top_n_out, *bounds)
+    else:  # a rule file: no search, no learn
         print("#Rules read: %d" % miner.read_rules(a.rule_file))
+        if a.stats_file is not None:
+            print("#Rule statistics written: %d" % miner.write_list_stats(a.stats_file, a.pc))
     for split in {None: (), "both": ("valid", "test")}.get(a.evaluate, (a.evaluate,)):
         print(metrics_line(split.capitalize(), miner.evaluate(split)))
 
