@@ -1463,11 +1463,12 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
     def all_rule_embeddings(self):
         """(num_rules, 16) embeddings of every rule, in rule-id order.  For
         type 'lstm' without autograd this is the fused HIP encoder
-        (rnnl_lstm_encode); otherwise the torch modules."""
+        (rnnl_lstm_encode_trie / rnnl_lstm_encode) where its kernels support
+        the model (_lstm_kernels); otherwise the torch modules."""
         if self.type == "emb":
             return self.rule_emb
         device = self.vocab_emb.weight.device
-        if self.type == "lstm" and device.type == "cuda" and not self._needs_grad():
+        if not self._needs_grad() and self._lstm_kernels(device, per_rule=not self.encoder_trie):
             return self._encode_rules_hip(device)
         return self.encode_rules(self.rule_features.to(device))
 
@@ -1562,8 +1563,8 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         w = hit[1] if hit is not None and hit[1].numel() == nbytes.value else \
             torch.empty(nbytes.value, dtype=torch.uint8, device=device)
         with torch.no_grad():
-            if (self.type == "lstm" and self.aggregator == "sum" and self.encoder_trie and device.type == "cuda"
-                    and not self._needs_grad()):
+            if (self.aggregator == "sum" and self.encoder_trie and not self._needs_grad()
+                    and self._lstm_kernels(device, per_rule=False)):
                 # the SUM records formed by the trie encoder's launches (rnnl_lstm_encode_trie_sum)
                 emb = self._encode_rules_hip(device, add_w, w)
             else:
@@ -2086,12 +2087,25 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
             return hit
         return torch.tensor([i for q in rels for i, _ in self.relation2rules[q]], dtype=torch.long, device=device)
 
+    def _lstm_kernels(self, device, per_rule=True):
+        """The rule encoder's HIP kernels (csrc/encode.hip) support this
+        model: an LSTM of their shape (hidden 16, 1-3 layers, with bias, one
+        direction, no projection) on a GPU and, for the forms with one lane
+        row per rule (rnnl_lstm_encode, the training kernels), rules of at
+        most 8 tokens — the trie form runs one launch per depth, of any
+        length.  The one predicate of the inference encoder
+        (all_rule_embeddings), the trie encoder's node records (node_weights)
+        and the training path (_lstm_hip); every other LSTM runs torch's."""
+        if self.type != "lstm" or device.type != "cuda":
+            return False
+        rnn = self.rnn
+        return (self.hidden_dim == 16 and rnn.hidden_size == 16 and 1 <= self.num_layers <= 3 and
+                rnn.num_layers == self.num_layers and bool(rnn.bias) and not rnn.bidirectional and
+                rnn.proj_size == 0 and (not per_rule or self.rule_features.size(1) <= 8))
+
     def _lstm_hip(self, device):
-        """The rule encoder's HIP training path applies: an LSTM of the fused
-        kernels' shape (hidden 16, 1-3 layers, rules of <= 7 tokens)."""
-        return (self.type == "lstm" and device.type == "cuda" and self.hidden_dim == 16 and
-                1 <= self.num_layers <= 3 and self.rule_features.size(1) <= 8 and self.rnn.bias and
-                not self.rnn.bidirectional and self.rnn.proj_size == 0)
+        """The rule encoder's HIP training path applies (_lstm_kernels)."""
+        return self._lstm_kernels(device, per_rule=True)
 
     def _token_csr(self, rels, device):
         """Per-token positions (row T + t) of the non-pad tokens of the rules of
