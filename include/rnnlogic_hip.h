@@ -707,6 +707,70 @@ int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const i
                         const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t *ranks,
                         double *val, uint64_t *counters, void *stream);
 
+/* ------------------------------------ the miner's answers and their rules --
+ * The first k tails of (h, r, ?) by the val of rnnl_miner_evaluate, and the
+ * rules that support each of them, with the rule lists and weights of the
+ * handle.  Tail queries only.  The n x n_entities matrix is never written.
+ *
+ *   rnnl_miner_predict: queries (device, n x 3 int32: h r t).  t >= 0 is the
+ *     known answer; t = -1 makes the query open: no edge is removed, no answer
+ *     is kept and position is -1.  val[e] is formed exactly as by
+ *     rnnl_miner_evaluate (list order, product then add, fp64, every edge equal
+ *     to (h, r, t) skipped on every hop): bitwise its val row.
+ *     An entity is reached when some rule with a non-empty body has a path
+ *     count > 0 there, whatever the rule's weight (a weight of 0.0 still
+ *     reaches).  Entity e is eligible when
+ *       candidates == RNNL_MINER_ALL, or e is reached (RNNL_MINER_REACHED), and
+ *       not (e != t and e is a known tail of (h, r)): known_keys / known_offs /
+ *         known_vals / n_keys as for rnnl_miner_evaluate, all three NULL:
+ *         nothing leaves; a tail listed twice leaves once, and
+ *       val[e] is not NaN.  (Finite weights give a NaN only through an
+ *         overflow to inf - inf; such an entity is never listed or counted.)
+ *     Order: val descending, then entity id ascending; -0.0 == +0.0, +-inf are
+ *     ordinary values (the order of rnnl_topk_rows).  index (device, n x k
+ *     int32) and score (device, n x k doubles) receive the first valid[i] =
+ *     min(k, #eligible) entities in that order and their stored val, bit for
+ *     bit; the remaining slots -1 and -inf.  position (device, n int32)
+ *     receives the 0-based place of t in the whole eligible order, whether or
+ *     not it is below k, or -1 when t is not eligible or the query is open.
+ *     The result is a function of the inputs alone.
+ *     1 <= k <= RNNL_MINER_TOPK_MAX.  counters (device, 4 x uint64, zeroed
+ *     here): [1] != 0: a path count does not fit u32 (RNNL_ERR_RANGE for the
+ *     caller to raise), [2] != 0: a query with h or r out of range, t < -1 or
+ *     t >= n_entities (its row is -1 / -inf, valid 0, position -1), [3]:
+ *     internal.
+ *   rnnl_miner_explain: the same queries; index (device, n x n_slots int32,
+ *     1 <= n_slots <= RNNL_MINER_TOPK_MAX) names one entity per slot, -1 an
+ *     unused slot (anything else out of range sets counters[2] and counts as
+ *     unused).  The query's rules are grounded again; per slot, over the rules
+ *     with a path count > 0 at the slot's entity, in list order:
+ *       fired (n x n_slots int32): how many there are;
+ *       total (n x n_slots doubles): the sum of weight * (double)count, bitwise
+ *         the entity's val and so the score of rnnl_miner_predict;
+ *       rule (n x n_slots x c int32): the c rules with the largest
+ *         contribution weight * count, descending, ties by list index
+ *         ascending (-0.0 == +0.0), as the index into relation r's list;
+ *         -1 where unused;
+ *       count (n x n_slots x c int64): the path count of each listed rule,
+ *         0 where unused.
+ *     1 <= c <= RNNL_MINER_EXPLAIN_MAX.  counters as above.
+ * A null handle, rules not set, k, n_slots or c out of range, or the known-tail
+ * arrays given partly are RNNL_ERR_INVALID with a message, decided before any
+ * device call.  Scratch for graphs of more than 512 entities is the handle's
+ * (shared with rnnl_miner_evaluate): one of the three calls per handle at a
+ * time.  Both are asynchronous on `stream`. */
+#define RNNL_MINER_TOPK_MAX 256
+#define RNNL_MINER_EXPLAIN_MAX 16
+#define RNNL_MINER_REACHED 0
+#define RNNL_MINER_ALL 1
+int rnnl_miner_predict(rnnl_miner m, const int32_t *queries, int64_t n, const int64_t *known_keys,
+                       const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t k,
+                       int32_t candidates, int32_t *index, double *score, int32_t *valid, int32_t *position,
+                       uint64_t *counters, void *stream);
+int rnnl_miner_explain(rnnl_miner m, const int32_t *queries, int64_t n, const int32_t *index, int32_t n_slots,
+                       int32_t c, int32_t *fired, double *total, int32_t *rule, int64_t *count, uint64_t *counters,
+                       void *stream);
+
 /* ------------------------------------- support and confidence of rules --
  * The exact counts behind standard and PCA confidence, on the handle's train
  * graph as given: no inverses, and — unlike search, learn and evaluate — no

@@ -116,6 +116,7 @@ struct rnnl_miner_s {
   int32_t ground_blocks = 0;
   unsigned char *eval_scratch = nullptr;  // rnnl_miner_evaluate above its LDS regime; one of bufs
   int32_t eval_blocks = 0;
+  unsigned char *pred_flags = nullptr;  // rnnl_miner_predict above the LDS regime: per workgroup a list (int) and a flag byte per entity
 };
 
 struct rnnl_graph_s {

@@ -22,23 +22,16 @@
 //
 // Up to EVAL_LDS_E entities val and the integer scratch live in LDS (104 bytes
 // per entity, sized by the graph), above that in a per-workgroup global
-// scratch kept in the handle.
+// scratch kept in the handle.  The grounding of a round and the round into val
+// are in mine_ground.h, which the predictions (mine_predict.hip) run as well.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "internal.h"
+#include "mine_ground.h"  // the layout, the grounding of a round and the round into val: shared with mine_predict.hip
 
 namespace rnnl {
-
-constexpr int EB = 256;          // threads per workgroup
-constexpr int EW = EB / 64;      // waves: rules grounded at once
-constexpr int EVAL_LDS_E = 512;  // everything in LDS up to this many entities (52 KiB)
-constexpr size_t EVAL_PER_E = 8 + EW * 24;  // val (f64) + per wave: counts A, B (u64), lists A, B (int)
-constexpr size_t EVAL_SCRATCH = 256u << 20;
-constexpr int EVAL_MAX_BLOCKS = 2048;
-
-enum : int { E_RANGE = 1, E_INVALID = 2, E_INTERNAL = 3 };
 
 struct EvalArgs {
   const int32_t *queries;
@@ -52,26 +45,6 @@ struct EvalArgs {
   unsigned long long *flags;
 };
 
-namespace {
-
-__device__ __forceinline__ unsigned long long eval_ld_u64(unsigned long long *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// first index in [lo, hi) of the (relation, target)-sorted edges with relation >= r
-__device__ __forceinline__ int eval_edge_lower(const int32_t *rel, int lo, int hi, int r) {
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (rel[mid] < r)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
-}  // namespace
-
 template <bool SMALL>
 __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, EvalArgs a) {
   extern __shared__ unsigned long long eval_smem[];
@@ -81,12 +54,7 @@ __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, E
                               : a.scratch + (size_t)blockIdx.x * EVAL_PER_E * (size_t)E;
   double *val = reinterpret_cast<double *>(base);
   unsigned char *ints = base + 8 * (size_t)E;  // wave w: counts A, counts B (u64 x E), list A, list B (int x E)
-  if (SMALL) {  // the global scratch is zeroed when it is allocated and left zeroed by every query
-    for (int i = tid; i < EW * 2 * E; i += EB) {
-      const int w = i / (2 * E);
-      reinterpret_cast<unsigned long long *>(ints + (size_t)w * 24 * (size_t)E)[i - w * 2 * E] = 0ull;
-    }
-  }
+  if (SMALL) eval_zero_ints(ints, E);
   __syncthreads();
 #pragma unroll 1
   for (int64_t qi = blockIdx.x; qi < a.n; qi += gridDim.x) {
@@ -105,73 +73,8 @@ __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, E
 #pragma unroll 1
     for (int jb = 0; jb < nr; jb += EW) {
       const int nw = min(EW, nr - jb);  // rules of this round
-      int mx = 0;
-      for (int w = 0; w < nw; ++w) mx = max(mx, l.rule_len[rb + jb + w]);
-      const int rule = rb + jb + wid;
-      const int len = wid < nw ? l.rule_len[rule] : 0;
-      unsigned long long *ca = reinterpret_cast<unsigned long long *>(ints + (size_t)wid * 24 * (size_t)E);
-      unsigned long long *cb = ca + E;
-      int *la = reinterpret_cast<int *>(cb + E), *lb = la + E;
-      int na = 0;
-      if (len > 0) {
-        if (lane == 0) {
-          la[0] = h;
-          ca[h] = 1;
-        }
-        na = 1;
-      }
-      for (int k = 0; k < mx; ++k) {
-        const bool act = k < len;
-        if (act && lane == 0) s_n[wid] = 0;
-        __syncthreads();
-        if (act) {
-          const int rel = l.rule_body[RULE_STRIDE * rule + k];
-          for (int i = lane; i < na; i += 64) {
-            const int e = la[i];
-            const unsigned long long n = eval_ld_u64(&ca[e]);
-            const int en = d.out_off[e + 1];
-            for (int b = eval_edge_lower(l.so_rel, d.out_off[e], en, rel); b < en && l.so_rel[b] == rel; ++b) {
-              const int x = l.so_dst[b];
-              if (e == h && rel == r && x == t) continue;  // the query's own edge, and every copy of it
-              wide |= n > 0xffffffffull;  // the paths through here alone are past 32 bits
-              if (atomicAdd(&cb[x], n) == 0) lb[atomicAdd(&s_n[wid], 1)] = x;
-            }
-          }
-        }
-        __syncthreads();
-        if (act) {
-          for (int i = lane; i < na; i += 64) ca[la[i]] = 0;
-          na = s_n[wid];
-          unsigned long long *tc = ca;
-          ca = cb;
-          cb = tc;
-          int *tl = la;
-          la = lb;
-          lb = tl;
-        }
-      }
-      if (lane == 0) s_na[wid] = na;
-      __syncthreads();
-      // the round's rules into val, one after the other: list order per destination
-      for (int w = 0; w < nw; ++w) {
-        const int len2 = l.rule_len[rb + jb + w];
-        if (len2 == 0) continue;  // an empty body reaches nothing
-        const double wt = l.wt[rb + jb + w];
-        unsigned long long *c0 = reinterpret_cast<unsigned long long *>(ints + (size_t)w * 24 * (size_t)E);
-        int *l0 = reinterpret_cast<int *>(c0 + 2 * (size_t)E);
-        unsigned long long *fc = (len2 & 1) ? c0 + E : c0;  // one swap per hop
-        const int *fl = (len2 & 1) ? l0 + E : l0;
-        const int n2 = s_na[w];
-        for (int i = tid; i < n2; i += EB) {
-          const int x = fl[i];
-          const unsigned long long c = eval_ld_u64(&fc[x]);
-          wide |= c > 0xffffffffull;
-          const double term = wt * (double)c;
-          val[x] = val[x] + term;
-          fc[x] = 0;
-        }
-        __syncthreads();
-      }
+      eval_ground_round(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
+      eval_round_into_val<false>(l, ints, E, rb, jb, nw, s_na, val, nullptr, nullptr, nullptr, wide);
     }
     if (wide) atomicOr(&a.flags[E_RANGE], 1ull);
     __syncthreads();
@@ -278,20 +181,8 @@ int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const i
     const unsigned grid = (unsigned)std::min<int64_t>(n, EVAL_MAX_BLOCKS);
     hipLaunchKernelGGL(eval_kernel<true>, dim3(grid), dim3(EB), EVAL_PER_E * E, st, m->d, m->l, a);
   } else {
-    if (!m->eval_scratch) {  // workgroups bounded by their scratch; zeroed once, every query leaves it zeroed
-      const int32_t blocks =
-          (int32_t)std::max<size_t>(16, std::min<size_t>(EVAL_MAX_BLOCKS, EVAL_SCRATCH / (EVAL_PER_E * E)));
-      void *p = nullptr;
-      if (hipMalloc(&p, (size_t)blocks * EVAL_PER_E * E) != hipSuccess) {
-        set_error("rnnl_miner_evaluate: device allocation failed");
-        return RNNL_ERR_NOMEM;
-      }
-      m->bufs.push_back(p);
-      RNNL_HIP_CHECK(hipMemset(p, 0, (size_t)blocks * EVAL_PER_E * E));
-      RNNL_HIP_CHECK(hipDeviceSynchronize());
-      m->eval_scratch = static_cast<unsigned char *>(p);
-      m->eval_blocks = blocks;
-    }
+    const int rc = eval_scratch_ensure(m, "rnnl_miner_evaluate");
+    if (rc != RNNL_OK) return rc;
     a.scratch = m->eval_scratch;
     const unsigned grid = (unsigned)std::min<int64_t>(n, m->eval_blocks);
     hipLaunchKernelGGL(eval_kernel<false>, dim3(grid), dim3(EB), 0, st, m->d, m->l, a);

@@ -19,6 +19,10 @@ running mean (RuleGenerator::update) and the rule file (out_rules)
     miner.evaluate("test")              # dict(mr, mrr, hit1, hit3, hit10, n), as ReasoningPredictor::evaluate
     miner.eval_ranks(triples); miner.scores(triples)   # the (num_g, num_ge) pairs / the val rows behind it
 
+    miner.predict_topk(queries, k=10)   # (h, r) or (h, r, t) -> device index, score, valid, position (filtered top-k)
+    miner.explain(queries, index, 3)    # per listed tail: fired, total, the 3 rules that contribute most, their counts
+    miner.predict("test", k=10, explain=3, output="pred.tsv")   # both, as numpy arrays and as a TSV file
+
     miner.rule_stats()                  # dict(support, body, pca_body): int64 per rule of the current lists (or of
     miner.pool_stats()                  # rel2rules given) / of the searched pool, in get_logic_rules() order
     miner.head_pairs(); miner.confidence("pca" | "std" | "head_coverage", pc=0.0)
@@ -29,6 +33,8 @@ running mean (RuleGenerator::update) and the rule file (out_rules)
     python -m rnnlogic_amd.miner -data-path D -output-file F -max-length 3 ...   # main.cpp's flags (-max-length 1..5)
     python -m rnnlogic_amd.miner -data-path D -output-file F ... -evaluate both  # + one metrics line per split
     python -m rnnlogic_amd.miner -data-path D -rule-file F -evaluate test        # evaluate a rule file, no mining
+    python -m rnnlogic_amd.miner -data-path D -rule-file F -predict test -predictions-file P -k 10 -explain 3
+    python -m rnnlogic_amd.miner -data-path D -rule-file F -queries-file Q -predictions-file P   # head<TAB>relation[<TAB>tail]
 
 The pool equals the reference's for the same train graph: every relation
 path of length <= max_length from h to t of a train triple (h, r, t), the
@@ -57,6 +63,14 @@ scores are the reference's bit for bit (fp64, product then add, rule list
 order per entity) and the two counts per triple — entities scoring above the
 tail, and at least as high — are exact, so the expectation over the tie run
 gives the reference's MR / MRR / HITS.
+
+predict_topk / explain / predict answer a query with the same scores
+(rnnl_miner_predict / rnnl_miner_explain, csrc/mine_predict.hip): the first k
+tails by val descending, then entity id, among the entities some rule reaches
+(or all), the other known tails of (h, r) left out; and per listed tail the
+rules with a path to it, their counts and the ones that contribute most.  The
+top k are selected inside the workgroup that built val, so the (n, |E|)
+matrix of `scores` is never written.  Tail queries only.
 """
 import ctypes
 import math
@@ -209,6 +223,39 @@ def expectation_metrics(ranks, n_entities):
 def metrics_line(name, m):
     return "%s | MR %.6f MRR %.6f HITS@1 %.6f @3 %.6f @10 %.6f" % (name, m["mr"], m["mrr"], m["hit1"], m["hit3"],
                                                                   m["hit10"])
+
+
+def _name(graph, table, i):
+    """The dictionary name of id i (graph.id2entity / id2relation), or the id itself where the graph has none."""
+    names = getattr(graph, table, None)
+    try:
+        return str(names[i])
+    except (TypeError, KeyError, IndexError):
+        return str(i)
+
+
+def read_queries_file(file_name, graph):
+    """Lines `head<TAB>relation` (open) or `head<TAB>relation<TAB>tail`, in the
+    names of the graph's dictionaries -> (n, 3) int64 with t = -1 for the open
+    ones.  An unknown name or a malformed line is a ValueError naming the line."""
+    out = []
+    with open(file_name) as fi:
+        for no, line in enumerate(fi, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            tok = line.split("\t")
+            if len(tok) not in (2, 3):
+                raise ValueError("%s:%d: expected head<TAB>relation or head<TAB>relation<TAB>tail" % (file_name, no))
+            if tok[0] not in graph.entity2id:
+                raise ValueError("%s:%d: unknown entity %r" % (file_name, no, tok[0]))
+            if tok[1] not in graph.relation2id:
+                raise ValueError("%s:%d: unknown relation %r" % (file_name, no, tok[1]))
+            if len(tok) == 3 and tok[2] not in graph.entity2id:
+                raise ValueError("%s:%d: unknown entity %r" % (file_name, no, tok[2]))
+            out.append((graph.entity2id[tok[0]], graph.relation2id[tok[1]],
+                        graph.entity2id[tok[2]] if len(tok) == 3 else -1))
+    return np.asarray(out, dtype=np.int64).reshape(-1, 3)
 
 
 def group_rules(head, ln, body, n_relations):
@@ -724,6 +771,150 @@ class RuleMiner(object):
             triples = getattr(self.graph, split + "_facts")
         return expectation_metrics(self.eval_ranks(triples, filtered), self.graph.entity_size)
 
+    # ----------------------------------------------------------- predictions
+    def _pred_queries(self, queries):
+        """(n, 2) (h, r) or (n, 3) (h, r, t) with t >= 0 or -1 -> (n, 3) int32, open queries with t = -1."""
+        q = np.asarray(queries, dtype=np.int64)
+        if q.size == 0:
+            q = q.reshape(0, 3)
+        if q.ndim != 2 or q.shape[1] not in (2, 3):
+            raise ValueError("queries must be (n, 2) (h, r) or (n, 3) (h, r, t) (got shape %r)" % (q.shape,))
+        if q.shape[1] == 2:
+            q = np.concatenate([q, np.full((len(q), 1), -1, dtype=np.int64)], 1)
+        E, R = self.graph.entity_size, self.graph.relation_size
+        if len(q) and (q[:, :2].min() < 0 or q[:, 0].max() >= E or q[:, 1].max() >= R or q[:, 2].min() < -1
+                       or q[:, 2].max() >= E):
+            raise ValueError("query out of range (h, t in [0, %d), r in [0, %d); t = -1: an open query)" % (E, R))
+        return np.ascontiguousarray(q, dtype=np.int32)
+
+    @torch.no_grad()
+    def predict_topk(self, queries, k=10, filtered=True, candidates="reached"):
+        """The first k tails of each query by the score of `scores` (val
+        descending, then entity id; rnnl_miner_predict, csrc/mine_predict.hip),
+        without the (n, |E|) matrix.  queries: (n, 2) (h, r) — open: no edge is
+        removed, no answer kept — or (n, 3) (h, r, t), t = -1 open as well.
+        candidates 'reached': the entities some rule reaches (whatever its
+        weight); 'all': every entity.  filtered: the other known tails of
+        (h, r) over train, valid and test leave, t stays.  Returns device
+        tensors: index (n, k) int32 (-1 past valid), score (n, k) float64
+        (bitwise `scores`; -inf past valid), valid (n,) int32 = min(k,
+        #eligible), position (n,) int32 = the 0-based place of t in the whole
+        eligible order (also past k), -1 if t is not eligible or the query is
+        open."""
+        k = int(k)
+        if not 1 <= k <= _native.MINER_TOPK_MAX:
+            raise ValueError("predict_topk: k must be 1..%d (got %d)" % (_native.MINER_TOPK_MAX, k))
+        if candidates not in ("reached", "all"):
+            raise ValueError("predict_topk: candidates must be 'reached' or 'all' (got %r)" % (candidates,))
+        q = self._pred_queries(queries)
+        n = len(q)
+        with torch.cuda.device(self.device):
+            qd = torch.from_numpy(q).to(self.device)
+            index = torch.empty((n, k), dtype=torch.int32, device=self.device)
+            score = torch.empty((n, k), dtype=torch.float64, device=self.device)
+            valid = torch.empty(n, dtype=torch.int32, device=self.device)
+            position = torch.empty(n, dtype=torch.int32, device=self.device)
+            kn = self._known_tails() if filtered else None
+            _native.call("rnnl_miner_predict", self._handle, qd.data_ptr(), n,
+                         kn.keys.data_ptr() if kn else None, kn.offs.data_ptr() if kn else None,
+                         kn.vals.data_ptr() if kn else None, kn.keys.numel() if kn else 0, k,
+                         _native.MINER_ALL if candidates == "all" else _native.MINER_REACHED, index.data_ptr(),
+                         score.data_ptr(), valid.data_ptr(), position.data_ptr(), self._counters.data_ptr(),
+                         torch.cuda.current_stream(self.device).cuda_stream)
+            self._check_counters()
+        return index, score, valid, position
+
+    @torch.no_grad()
+    def explain(self, queries, index, rules_per_tail=3):
+        """The rules behind the entities index (n, m) int32 (-1: an unused
+        slot; m <= 256) of each query (rnnl_miner_explain).  Returns device
+        tensors: fired (n, m) int32 = the rules with a path to the entity,
+        total (n, m) float64 = their weight * count summed in list order
+        (bitwise the entity's score), rule (n, m, c) int32 = the c =
+        rules_per_tail (1..16) rules with the largest weight * count, ties by
+        list index, as indices into the relation's rule list (-1 unused), and
+        count (n, m, c) int64 = their path counts."""
+        c = int(rules_per_tail)
+        if not 1 <= c <= _native.MINER_EXPLAIN_MAX:
+            raise ValueError("explain: rules_per_tail must be 1..%d (got %d)" % (_native.MINER_EXPLAIN_MAX, c))
+        q = self._pred_queries(queries)
+        n = len(q)
+        with torch.cuda.device(self.device):
+            idx = torch.as_tensor(index, device=self.device).to(torch.int32).contiguous()
+            if idx.dim() != 2 or idx.shape[0] != n or not 1 <= idx.shape[1] <= _native.MINER_TOPK_MAX:
+                raise ValueError("explain: index must be (n, m) with 1 <= m <= %d (got %r for %d queries)"
+                                 % (_native.MINER_TOPK_MAX, tuple(idx.shape), n))
+            m = idx.shape[1]
+            qd = torch.from_numpy(q).to(self.device)
+            fired = torch.empty((n, m), dtype=torch.int32, device=self.device)
+            total = torch.empty((n, m), dtype=torch.float64, device=self.device)
+            rule = torch.empty((n, m, c), dtype=torch.int32, device=self.device)
+            count = torch.empty((n, m, c), dtype=torch.int64, device=self.device)
+            _native.call("rnnl_miner_explain", self._handle, qd.data_ptr(), n, idx.data_ptr(), m, c,
+                         fired.data_ptr(), total.data_ptr(), rule.data_ptr(), count.data_ptr(),
+                         self._counters.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+            self._check_counters()
+        return fired, total, rule, count
+
+    def predict(self, split="test", triples=None, k=10, filtered=True, explain=0, rules_per_tail=3,
+                candidates="reached", output=None):
+        """The miner's answers on graph.valid_facts / test_facts (split
+        'valid' / 'test') or the given queries ((n, 2) or (n, 3), as
+        predict_topk), with the current rules and weights.  Returns a dict of
+        numpy arrays: h, r, t (n,), index / score (n, k), valid, position (n,)
+        and, with explain = m > 0, explain_fired / explain_total (n, m') and
+        explain_rule / explain_count (n, m', rules_per_tail) of the first m' =
+        min(m, k) places (`explain`).  output: one TSV line per prediction —
+        head, relation, place (1-based), tail, repr(score), `*` on the known
+        answer, then for the explained places `head <- b1, b2:count:weight`
+        per listed rule, names from the graph's dictionaries."""
+        if triples is None:
+            if split not in ("valid", "test"):
+                raise ValueError("predict: split must be 'valid' or 'test'")
+            triples = getattr(self.graph, split + "_facts")
+        q = self._pred_queries(triples)
+        index, score, valid, position = self.predict_topk(q, k, filtered, candidates)
+        out = dict(h=q[:, 0].astype(np.int64), r=q[:, 1].astype(np.int64), t=q[:, 2].astype(np.int64),
+                   index=index.cpu().numpy(), score=score.cpu().numpy(), valid=valid.cpu().numpy(),
+                   position=position.cpu().numpy())
+        m = min(int(explain), int(k))
+        if m > 0:
+            names = ("explain_fired", "explain_total", "explain_rule", "explain_count")
+            if len(q):
+                got = self.explain(q, index[:, :m].contiguous(), rules_per_tail)
+                out.update((name, v.cpu().numpy()) for name, v in zip(names, got))
+            else:
+                c = int(rules_per_tail)
+                out.update(zip(names, (np.zeros((0, m), np.int32), np.zeros((0, m), np.float64),
+                                       np.zeros((0, m, c), np.int32), np.zeros((0, m, c), np.int64))))
+        if output is not None:
+            self._write_predictions(output, out, m)
+        return out
+
+    def rule_text(self, r, k, count=None, weight=None):
+        """Rule k of relation r's list in relation names: `head <- b1, b2` (`:count:weight` appended if given)."""
+        i = int(self._rule_off[r]) + int(k)
+        body = self._rule_body[i][:int(self._rule_len[i])].tolist()
+        text = "%s <- %s" % (_name(self.graph, "id2relation", r),
+                             ", ".join(_name(self.graph, "id2relation", b) for b in body))
+        return text if count is None else "%s:%d:%r" % (text, count, float(weight))
+
+    def _write_predictions(self, path, out, m):
+        wt = self.weights() if m > 0 else None
+        with open(path, "w") as fo:
+            for i in range(len(out["h"])):
+                h, r, t = int(out["h"][i]), int(out["r"][i]), int(out["t"][i])
+                for j in range(int(out["valid"][i])):
+                    e = int(out["index"][i, j])
+                    cols = [_name(self.graph, "id2entity", h), _name(self.graph, "id2relation", r), str(j + 1),
+                            _name(self.graph, "id2entity", e), repr(float(out["score"][i, j])), "*" if e == t else ""]
+                    if j < m:
+                        cols += [self.rule_text(r, kk, c, wt[r][kk]) for kk, c in
+                                 zip(out["explain_rule"][i, j].tolist(), out["explain_count"][i, j].tolist())
+                                 if kk >= 0]
+                    fo.write("\t".join(cols) + "\n")
+        return int(np.sum(out["valid"]))
+
     def mine(self, max_length, iterations, top_n, top_k, lr, wd, temp, top_n_out=0, seed=0, orders=None,
              selections=None, portion=1.0, prior=None, prior_weight=0.0, pc=0.0):
         """The reference miner's main loop (miner/main.cpp:27-49): search, then
@@ -883,11 +1074,28 @@ def main(argv=None):
     ap.add_argument("-pc", dest="pc", type=float, default=0.0)
     ap.add_argument("-prior", dest="prior", choices=["std", "pca"], default=None)
     ap.add_argument("-prior-weight", dest="prior_weight", type=float, default=0.0)
+    ap.add_argument("-predict", dest="predict", choices=["valid", "test"], default=None)
+    ap.add_argument("-queries-file", dest="queries_file", default=None)
+    ap.add_argument("-predictions-file", dest="predictions_file", default=None)
+    ap.add_argument("-k", dest="k", type=int, default=10)
+    ap.add_argument("-explain", dest="explain", type=int, default=0)
+    ap.add_argument("-rules-per-tail", dest="rules_per_tail", type=int, default=3)
+    ap.add_argument("-candidates", dest="candidates", choices=["reached", "all"], default="reached")
     a = ap.parse_args(argv)
+    predicting = a.predict is not None or a.queries_file is not None
     if a.output_file is None and a.rule_file is None:
         ap.error("the following arguments are required: -output-file")
-    if a.rule_file is not None and (a.output_file is not None or (a.evaluate is None and a.stats_file is None)):
-        ap.error("-rule-file evaluates a rule file: give -evaluate, and no -output-file")
+    if a.rule_file is not None and (a.output_file is not None
+                                    or (a.evaluate is None and a.stats_file is None and not predicting)):
+        ap.error("-rule-file evaluates a rule file: give -evaluate, -predict or -queries-file, and no -output-file")
+    if a.predict is not None and a.queries_file is not None:
+        ap.error("-predict takes a split, -queries-file a file of queries: give one of them")
+    if predicting != (a.predictions_file is not None):
+        ap.error("-predict / -queries-file write their answers to -predictions-file: give both or neither")
+    if predicting and not 1 <= a.k <= _native.MINER_TOPK_MAX:
+        ap.error("-k must be 1..%d" % _native.MINER_TOPK_MAX)
+    if predicting and (a.explain < 0 or not 1 <= a.rules_per_tail <= _native.MINER_EXPLAIN_MAX):
+        ap.error("-explain must be >= 0 and -rules-per-tail 1..%d" % _native.MINER_EXPLAIN_MAX)
     if a.rule_file is None and not 1 <= a.max_length <= MAX_BODY:
         ap.error("-max-length must be 1..%d" % MAX_BODY)
     if a.pc < 0.0 or a.min_support < 0:
@@ -897,6 +1105,8 @@ def main(argv=None):
     # mining: bodies as long as asked for; a rule file: as long as the miner holds
     miner = RuleMiner(KnowledgeGraph(a.data_path),
                       max_body=MAX_BODY if a.rule_file is not None else max(3, a.max_length))
+    # (a name the dictionaries do not know stops the run before it mines)
+    queries = read_queries_file(a.queries_file, miner.graph) if a.queries_file is not None else None
     if a.output_file is not None:
         miner.mine(a.max_length, a.iterations, a.top_n, a.top_k, a.lr, a.wd, a.temp, a.top_n_out, seed=a.seed,
                    prior=a.prior, prior_weight=a.prior_weight, pc=a.pc)
@@ -910,6 +1120,10 @@ def main(argv=None):
             print("#Rule statistics written: %d" % miner.write_list_stats(a.stats_file, a.pc))
     for split in {None: (), "both": ("valid", "test")}.get(a.evaluate, (a.evaluate,)):
         print(metrics_line(split.capitalize(), miner.evaluate(split)))
+    if predicting:
+        out = miner.predict(a.predict, queries, a.k, True, a.explain, a.rules_per_tail, a.candidates,
+                            a.predictions_file)
+        print("#Predictions written: %d" % int(np.sum(out["valid"])))
 
 
 if __name__ == "__main__":
