@@ -701,16 +701,36 @@ int rnnl_miner_read(rnnl_miner m, double *weights, double *H, void *stream);
  *     (its ranks are 0 0, its val row is not written), [3]: internal.
  *     Scratch for graphs of more than 512 entities is kept in the handle: one
  *     evaluation per handle at a time.
- * Both are asynchronous on `stream`. */
+ *   rnnl_miner_evaluate_side: side RNNL_MINER_TAIL is rnnl_miner_evaluate.
+ *     RNNL_MINER_HEAD answers the same triples on the head side, (?, r, t):
+ *     val[e] = sum over relation r's rules k in list order of weight[k] *
+ *     (double)(number of paths from e to t along rule k's body), every edge
+ *     equal to (h, r, t) skipped on every hop (the same fixed edge as on the
+ *     tail side, whatever e is); fp64, product then add, in list order per
+ *     entity, no floating-point atomics.  An entity e is skipped when e != h and
+ *     e is a known head of (r, t): known_keys are r * n_entities + t, known_vals
+ *     the heads, ascending within a key.  ranks receives num_g / num_ge against
+ *     val[h]; h itself always counts.  val, counters and [2] (h, t or r out of
+ *     range) as above.  With G' the graph of the triples (t, r, h) and every
+ *     body reversed, the head-side val of (h, r, t) on G is bitwise the
+ *     tail-side val of (t, r, h) on G'.  Any other side is RNNL_ERR_INVALID,
+ *     decided before any device call.
+ * All are asynchronous on `stream`. */
+#define RNNL_MINER_TAIL 0
+#define RNNL_MINER_HEAD 1
 int rnnl_miner_set_weights(rnnl_miner m, const double *weights, void *stream);
 int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const int64_t *known_keys,
                         const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t *ranks,
                         double *val, uint64_t *counters, void *stream);
+int rnnl_miner_evaluate_side(rnnl_miner m, int32_t side, const int32_t *queries, int64_t n,
+                             const int64_t *known_keys, const int64_t *known_offs, const int32_t *known_vals,
+                             int64_t n_keys, int32_t *ranks, double *val, uint64_t *counters, void *stream);
 
 /* ------------------------------------ the miner's answers and their rules --
  * The first k tails of (h, r, ?) by the val of rnnl_miner_evaluate, and the
  * rules that support each of them, with the rule lists and weights of the
- * handle.  Tail queries only.  The n x n_entities matrix is never written.
+ * handle; rnnl_miner_predict_side / rnnl_miner_explain_side answer (?, r, t)
+ * as well (below).  The n x n_entities matrix is never written.
  *
  *   rnnl_miner_predict: queries (device, n x 3 int32: h r t).  t >= 0 is the
  *     known answer; t = -1 makes the query open: no edge is removed, no answer
@@ -754,11 +774,22 @@ int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const i
  *       count (n x n_slots x c int64): the path count of each listed rule,
  *         0 where unused.
  *     1 <= c <= RNNL_MINER_EXPLAIN_MAX.  counters as above.
- * A null handle, rules not set, k, n_slots or c out of range, or the known-tail
- * arrays given partly are RNNL_ERR_INVALID with a message, decided before any
- * device call.  Scratch for graphs of more than 512 entities is the handle's
- * (shared with rnnl_miner_evaluate): one of the three calls per handle at a
- * time.  Both are asynchronous on `stream`. */
+ *   rnnl_miner_predict_side / rnnl_miner_explain_side: side RNNL_MINER_TAIL is
+ *     the two calls above.  RNNL_MINER_HEAD: the first k heads of (?, r, t) and
+ *     the rules behind them.  Everything above reads with h and t exchanging
+ *     roles: val[e] is the head-side val of rnnl_miner_evaluate_side (paths
+ *     from e to t, every edge equal to (h, r, t) skipped on every hop), bitwise;
+ *     h >= 0 is the known answer, h = -1 makes the query open (no edge is
+ *     removed, no answer is kept, position is -1); e leaves when e != h and e
+ *     is a known head of (r, t) (keys r * n_entities + t, heads ascending
+ *     within a key); position is the place of h; counters[2]: t or r out of
+ *     range, h < -1 or h >= n_entities.  fired / total / rule / count read the
+ *     path counts from the slot's entity to t.
+ * A null handle, rules not set, an unknown side, k, n_slots or c out of range,
+ * or the known-answer arrays given partly are RNNL_ERR_INVALID with a message,
+ * decided before any device call.  Scratch for graphs of more than 512
+ * entities is the handle's (shared with rnnl_miner_evaluate): one of these
+ * calls per handle at a time.  All are asynchronous on `stream`. */
 #define RNNL_MINER_TOPK_MAX 256
 #define RNNL_MINER_EXPLAIN_MAX 16
 #define RNNL_MINER_REACHED 0
@@ -770,6 +801,13 @@ int rnnl_miner_predict(rnnl_miner m, const int32_t *queries, int64_t n, const in
 int rnnl_miner_explain(rnnl_miner m, const int32_t *queries, int64_t n, const int32_t *index, int32_t n_slots,
                        int32_t c, int32_t *fired, double *total, int32_t *rule, int64_t *count, uint64_t *counters,
                        void *stream);
+int rnnl_miner_predict_side(rnnl_miner m, int32_t side, const int32_t *queries, int64_t n, const int64_t *known_keys,
+                            const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t k,
+                            int32_t candidates, int32_t *index, double *score, int32_t *valid, int32_t *position,
+                            uint64_t *counters, void *stream);
+int rnnl_miner_explain_side(rnnl_miner m, int32_t side, const int32_t *queries, int64_t n, const int32_t *index,
+                            int32_t n_slots, int32_t c, int32_t *fired, double *total, int32_t *rule, int64_t *count,
+                            uint64_t *counters, void *stream);
 
 /* ------------------------------------- support and confidence of rules --
  * The exact counts behind standard and PCA confidence, on the handle's train

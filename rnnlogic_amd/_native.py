@@ -23,6 +23,7 @@ TOPK_MAX = 1024  # RNNL_TOPK_MAX
 KGE_TAIL, KGE_HEAD = 0, 1
 MINER_TOPK_MAX, MINER_EXPLAIN_MAX = 256, 16  # RNNL_MINER_TOPK_MAX, RNNL_MINER_EXPLAIN_MAX
 MINER_REACHED, MINER_ALL = 0, 1
+MINER_TAIL, MINER_HEAD = 0, 1  # RNNL_MINER_TAIL, RNNL_MINER_HEAD
 
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -121,6 +122,10 @@ SIGNATURES = [
     ("rnnl_miner_evaluate", ctypes.c_int, [_P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P]),
     ("rnnl_miner_predict", ctypes.c_int, [_P, _P, _I64, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     ("rnnl_miner_explain", ctypes.c_int, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    ("rnnl_miner_evaluate_side", ctypes.c_int, [_P, _I32, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    ("rnnl_miner_predict_side", ctypes.c_int,
+     [_P, _I32, _P, _I64, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    ("rnnl_miner_explain_side", ctypes.c_int, [_P, _I32, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     ("rnnl_miner_rule_stats_scratch", ctypes.c_int, [_P, _I64, _I64, _I32, _P]),
     ("rnnl_miner_rule_stats", ctypes.c_int,
      [_P, _I64, _P, _P, _P, _P, _I32, ctypes.c_uint32, _P, ctypes.c_size_t, _P, _P, _P]),

@@ -42,11 +42,14 @@ struct MinerDev {
 
 // What the miner's learn / H_score stage adds to the handle (mine_learn.hip):
 // the out-edges once more, sorted by (source, relation, target) under the same
-// out_off, the current rule lists and one Adam parameter + H per rule.
+// out_off, the in-edges once more, sorted by (target, relation, source) under
+// in_off (the head side of mine_ground.h), the current rule lists and one Adam
+// parameter + H per rule.
 constexpr int RULE_STRIDE = 5;  // body relations stored per rule: the longest body
 
 struct MinerLearnDev {
   const int32_t *so_rel = nullptr, *so_dst = nullptr;  // n, n
+  const int32_t *si_rel = nullptr, *si_src = nullptr;  // n, n
   int32_t n_rules = 0;
   const int32_t *rule_off = nullptr;   // R + 1: relation r's rules are [rule_off[r], rule_off[r + 1])
   const int32_t *rule_len = nullptr;   // n_rules, 0..RULE_STRIDE

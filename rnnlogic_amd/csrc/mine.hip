@@ -529,8 +529,22 @@ int rnnl_miner_create(const int32_t *hrt, int64_t n, int32_t E, int32_t R, rnnl_
       }
     }
   }
+  // and the in-edges once more, sorted by (relation, source) within a target (the head side of mine_ground.h)
+  std::vector<int32_t> si_rel(n), si_src(n);
+  {
+    std::vector<std::pair<int32_t, int32_t>> tmp;
+    for (int32_t e = 0; e < E; ++e) {
+      tmp.clear();
+      for (int32_t k = in_off[e]; k < in_off[e + 1]; ++k) tmp.emplace_back(in_rel[k], in_src[k]);
+      std::sort(tmp.begin(), tmp.end());
+      for (size_t k = 0; k < tmp.size(); ++k) {
+        si_rel[in_off[e] + k] = tmp[k].first;
+        si_src[in_off[e] + k] = tmp[k].second;
+      }
+    }
+  }
   rnnl_miner_s *mm = new rnnl_miner_s;
-  auto up = [&](const std::vector<int32_t> &v, const int32_t *&dst) -> int {
+  auto up =[&](const std::vector<int32_t> &v, const int32_t *&dst) -> int {
     void *p = nullptr;
     const size_t bytes = std::max<size_t>(4, v.size() * 4);
     if (hipMalloc(&p, bytes) != hipSuccess) return RNNL_ERR_NOMEM;
@@ -547,7 +561,8 @@ int rnnl_miner_create(const int32_t *hrt, int64_t n, int32_t E, int32_t R, rnnl_
                   std::make_pair(&out_rel, &mm->d.out_rel), std::make_pair(&in_off, &mm->d.in_off),
                   std::make_pair(&in_src, &mm->d.in_src), std::make_pair(&in_rel, &mm->d.in_rel),
                   std::make_pair(&th, &mm->d.th), std::make_pair(&tr, &mm->d.tr), std::make_pair(&tt, &mm->d.tt),
-                  std::make_pair(&so_rel, &mm->l.so_rel), std::make_pair(&so_dst, &mm->l.so_dst)})
+                  std::make_pair(&so_rel, &mm->l.so_rel), std::make_pair(&so_dst, &mm->l.so_dst),
+                  std::make_pair(&si_rel, &mm->l.si_rel), std::make_pair(&si_src, &mm->l.si_src)})
     if (rc == RNNL_OK) rc = up(*pr.first, *pr.second);
   if (rc != RNNL_OK) {
     for (void *p : mm->bufs) (void)hipFree(p);

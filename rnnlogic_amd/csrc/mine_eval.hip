@@ -24,6 +24,12 @@
 // per entity, sized by the graph), above that in a per-workgroup global
 // scratch kept in the handle.  The grounding of a round and the round into val
 // are in mine_ground.h, which the predictions (mine_predict.hip) run as well.
+//
+// The head side (rnnl_miner_evaluate_side with RNNL_MINER_HEAD):
+// val[e] = sum of wt[k] * (double)#paths(e -> t along the body), grounded
+// backward from t over the in-edges; h is the answer, the known lists are the
+// known heads of (r, t).  The same kernel with h and t exchanging roles: `anc`
+// is the end the grounding starts at, `ans` the answer's end.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,7 +51,7 @@ struct EvalArgs {
   unsigned long long *flags;
 };
 
-template <bool SMALL>
+template <bool SMALL, bool HEAD>
 __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, EvalArgs a) {
   extern __shared__ unsigned long long eval_smem[];
   __shared__ int s_n[EW], s_na[EW], s_g[EW], s_ge[EW];
@@ -67,29 +73,30 @@ __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, E
       }
       continue;
     }
+    const int anc = HEAD ? t : h, ans = HEAD ? h : t;
     for (int x = tid; x < E; x += EB) val[x] = 0.0;
     const int rb = l.rule_off[r], nr = l.rule_off[r + 1] - rb;
     bool wide = false;
 #pragma unroll 1
     for (int jb = 0; jb < nr; jb += EW) {
       const int nw = min(EW, nr - jb);  // rules of this round
-      eval_ground_round(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
+      eval_ground_round<HEAD>(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
       eval_round_into_val<false>(l, ints, E, rb, jb, nw, s_na, val, nullptr, nullptr, nullptr, wide);
     }
     if (wide) atomicOr(&a.flags[E_RANGE], 1ull);
     __syncthreads();
-    const double t_val = val[t];
+    const double t_val = val[ans];
     int g = 0, ge = 0;
     for (int x = tid; x < E; x += EB) {
       const double v = val[x];
       if (a.val_out) a.val_out[qi * (int64_t)E + x] = v;
-      if (x != t) {
+      if (x != ans) {
         g += v > t_val;
         ge += v >= t_val;
       }
     }
-    if (a.known_keys) {  // minus the other known tails of (h, r)
-      const int64_t key = (int64_t)r * E + h;
+    if (a.known_keys) {  // minus the other known tails of (h, r) / known heads of (r, t)
+      const int64_t key = (int64_t)r * E + anc;
       int64_t lo = 0, hi = a.n_keys;
       while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
@@ -102,7 +109,7 @@ __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, E
         const int64_t b0 = a.known_offs[lo], b1 = a.known_offs[lo + 1];
         for (int64_t i = b0 + tid; i < b1; i += EB) {
           const int e = a.known_vals[i];
-          if ((unsigned)e >= (unsigned)E || e == t || (i > b0 && a.known_vals[i - 1] == e)) continue;
+          if ((unsigned)e >= (unsigned)E || e == ans || (i > b0 && a.known_vals[i - 1] == e)) continue;
           const double v = val[e];
           g -= v > t_val;
           ge -= v >= t_val;
@@ -120,7 +127,7 @@ __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, E
     }
     __syncthreads();
     if (tid == 0) {
-      int sg = 0, sge = 1;  // the tail itself always counts
+      int sg = 0, sge = 1;  // the answer itself always counts
       for (int w = 0; w < EW; ++w) {
         sg += s_g[w];
         sge += s_ge[w];
@@ -152,13 +159,18 @@ int rnnl_miner_set_weights(rnnl_miner m, const double *weights, void *stream) {
   return RNNL_OK;
 }
 
-int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const int64_t *known_keys,
-                        const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t *ranks,
-                        double *val, uint64_t *counters, void *stream) {
+int rnnl_miner_evaluate_side(rnnl_miner m, int32_t side, const int32_t *queries, int64_t n,
+                             const int64_t *known_keys, const int64_t *known_offs, const int32_t *known_vals,
+                             int64_t n_keys, int32_t *ranks, double *val, uint64_t *counters, void *stream) {
+  if (side != RNNL_MINER_TAIL && side != RNNL_MINER_HEAD) {
+    set_error("rnnl_miner_evaluate_side: side must be RNNL_MINER_TAIL or RNNL_MINER_HEAD");
+    return RNNL_ERR_INVALID;
+  }
+  const bool head = side == RNNL_MINER_HEAD;
   const bool none = !known_keys && !known_offs && !known_vals;
   const bool all = known_keys && known_offs && known_vals && n_keys >= 0;
   if (!m || !m->l.rule_off || n < 0 || (n > 0 && (!queries || !ranks)) || !counters || !(none || all)) {
-    set_error("rnnl_miner_evaluate: bad arguments (set the rules first; the known-tail arrays all or none)");
+    set_error("rnnl_miner_evaluate: bad arguments (set the rules first; the known-answer arrays all or none)");
     return RNNL_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -179,16 +191,25 @@ int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const i
   const size_t E = (size_t)m->d.E;
   if (m->d.E <= EVAL_LDS_E) {
     const unsigned grid = (unsigned)std::min<int64_t>(n, EVAL_MAX_BLOCKS);
-    hipLaunchKernelGGL(eval_kernel<true>, dim3(grid), dim3(EB), EVAL_PER_E * E, st, m->d, m->l, a);
+    auto kernel = head ? eval_kernel<true, true> : eval_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), EVAL_PER_E * E, st, m->d, m->l, a);
   } else {
     const int rc = eval_scratch_ensure(m, "rnnl_miner_evaluate");
     if (rc != RNNL_OK) return rc;
     a.scratch = m->eval_scratch;
     const unsigned grid = (unsigned)std::min<int64_t>(n, m->eval_blocks);
-    hipLaunchKernelGGL(eval_kernel<false>, dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
+    auto kernel = head ? eval_kernel<false, true> : eval_kernel<false, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
   }
   RNNL_HIP_CHECK(hipGetLastError());
   return RNNL_OK;
+}
+
+int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const int64_t *known_keys,
+                        const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t *ranks,
+                        double *val, uint64_t *counters, void *stream) {
+  return rnnl_miner_evaluate_side(m, RNNL_MINER_TAIL, queries, n, known_keys, known_offs, known_vals, n_keys, ranks,
+                                  val, counters, stream);
 }
 
 }  // extern "C"

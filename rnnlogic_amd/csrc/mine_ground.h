@@ -31,7 +31,7 @@ __device__ __forceinline__ unsigned long long eval_ld_u64(unsigned long long *p)
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// first index in [lo, hi) of the (relation, target)-sorted edges with relation >= r
+// first index in [lo, hi) of the (relation, other end)-sorted edges with relation >= r
 __device__ __forceinline__ int eval_edge_lower(const int32_t *rel, int lo, int hi, int r) {
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
@@ -52,16 +52,25 @@ __device__ __forceinline__ void eval_zero_ints(unsigned char *ints, int E) {
   }
 }
 
-// Grounds rules rb + jb .. rb + jb + nw - 1 (nw <= EW) of relation r from h,
-// wave w rule jb + w: frontier list + dense u64 path counts per hop in the
-// wave's integer scratch, integer atomics only; every edge equal to (h, r, t)
-// skipped on every hop (t = -1: none is).  On return s_na[w] is the number of
-// destinations of wave w's rule; its list and counts are in the half of the
-// scratch that (length & 1) names.  Called by the whole workgroup.
+// Grounds rules rb + jb .. rb + jb + nw - 1 (nw <= EW) of relation r, wave w
+// rule jb + w: frontier list + dense u64 path counts per hop in the wave's
+// integer scratch, integer atomics only; every edge equal to (h, r, t) skipped
+// on every hop.  Tail side (HEAD false): forward from h along the body over the
+// out-edges (so_*), t = -1: no edge is skipped.  Head side: backward from t,
+// hop k takes body[len - 1 - k] over the in-edges (si_*, under in_off), so the
+// count at e is #paths(e -> t along the body); h = -1: no edge is skipped.  On
+// return s_na[w] is the number of destinations of wave w's rule; its list and
+// counts are in the half of the scratch that (length & 1) names.  Called by the
+// whole workgroup.
+template <bool HEAD>
 __device__ __forceinline__ void eval_ground_round(const MinerDev &d, const MinerLearnDev &l, unsigned char *ints,
                                                   int h, int r, int t, int rb, int jb, int nw, int *s_n, int *s_na,
                                                   bool &wide) {
   const int E = d.E, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int32_t *e_off = HEAD ? d.in_off : d.out_off;   // the edges of an entity on this side,
+  const int32_t *e_rel = HEAD ? l.si_rel : l.so_rel;    // sorted by (relation, other end)
+  const int32_t *e_end = HEAD ? l.si_src : l.so_dst;
+  const int start = HEAD ? t : h;
   int mx = 0;
   for (int w = 0; w < nw; ++w) mx = max(mx, l.rule_len[rb + jb + w]);
   const int rule = rb + jb + wid;
@@ -72,8 +81,8 @@ __device__ __forceinline__ void eval_ground_round(const MinerDev &d, const Miner
   int na = 0;
   if (len > 0) {
     if (lane == 0) {
-      la[0] = h;
-      ca[h] = 1;
+      la[0] = start;
+      ca[start] = 1;
     }
     na = 1;
   }
@@ -82,14 +91,15 @@ __device__ __forceinline__ void eval_ground_round(const MinerDev &d, const Miner
     if (act && lane == 0) s_n[wid] = 0;
     __syncthreads();
     if (act) {
-      const int rel = l.rule_body[RULE_STRIDE * rule + k];
+      const int rel = l.rule_body[RULE_STRIDE * rule + (HEAD ? len - 1 - k : k)];
       for (int i = lane; i < na; i += 64) {
         const int e = la[i];
         const unsigned long long n = eval_ld_u64(&ca[e]);
-        const int en = d.out_off[e + 1];
-        for (int b = eval_edge_lower(l.so_rel, d.out_off[e], en, rel); b < en && l.so_rel[b] == rel; ++b) {
-          const int x = l.so_dst[b];
-          if (e == h && rel == r && x == t) continue;  // the query's own edge, and every copy of it
+        const int en = e_off[e + 1];
+        for (int b = eval_edge_lower(e_rel, e_off[e], en, rel); b < en && e_rel[b] == rel; ++b) {
+          const int x = e_end[b];
+          // the query's own edge, and every copy of it: (e, rel, x) forward, (x, rel, e) backward
+          if (rel == r && (HEAD ? (x == h && e == t) : (e == h && x == t))) continue;
           wide |= n > 0xffffffffull;  // the paths through here alone are past 32 bits
           if (atomicAdd(&cb[x], n) == 0) lb[atomicAdd(&s_n[wid], 1)] = x;
         }

@@ -545,6 +545,8 @@ static int set_rules_impl(rnnl_miner m, const int32_t *rule_off, const int32_t *
   m->l = rnnl::MinerLearnDev();
   m->l.so_rel = keep.so_rel;
   m->l.so_dst = keep.so_dst;
+  m->l.si_rel = keep.si_rel;
+  m->l.si_src = keep.si_src;
   m->l.n_rules = n;
   // workgroups of the grounding pass: bounded by their scratch (24 bytes per entity each)
   m->ground_blocks = (int32_t)std::max<size_t>(64, std::min<size_t>(4096, GROUND_SCRATCH / (24 * (size_t)E)));

@@ -44,6 +44,13 @@
 // in the output arrays (insertion, no LDS, no atomics).  total adds
 // wt * (double)count in list order, as val does.
 //
+// The head side (rnnl_miner_predict_side / rnnl_miner_explain_side
+// with RNNL_MINER_HEAD): the first k heads of (?, r, t).  val is grounded
+// backward from t (mine_ground.h), the known lists are the known heads of
+// (r, t), and h is the answer, -1 when the query is open.  The same kernels
+// with `anc` the end the grounding starts at and `ans` the answer's end;
+// everything from eligibility on reads as on the tail side.
+//
 // LDS, EVAL_LDS_E = 512 entities: 52 KiB of eval_kernel's arrays + the list
 // (2 KiB) + 512 flag bytes + the histogram, the sort buffer and counters
 // (4.1 KiB): 58.6 KiB, under 64 KiB.
@@ -100,23 +107,24 @@ __device__ __forceinline__ bool pred_before(unsigned long long ka, int ea, unsig
   return ka > kb || (ka == kb && ea < eb);
 }
 
-__device__ __forceinline__ bool query_bad(int h, int r, int t, int E, int R) {
-  return (unsigned)h >= (unsigned)E || (unsigned)r >= (unsigned)R || t < -1 || t >= E;
+// anc: the end the grounding starts at; ans: the answer's end, -1 in an open query
+__device__ __forceinline__ bool query_bad(int anc, int r, int ans, int E, int R) {
+  return (unsigned)anc >= (unsigned)E || (unsigned)r >= (unsigned)R || ans < -1 || ans >= E;
 }
 
 }  // namespace
 
 enum : int { C_TOUCHED, C_ELIG, C_AHEAD, C_SURV, C_KNOWN, C_KNOWN_LT, C_TOUCHED_LT, C_CAND, C_N };
 
-template <bool SMALL>
+template <bool SMALL, bool HEAD>
 __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l, PredArgs a) {
   extern __shared__ unsigned long long eval_smem[];
   __shared__ int s_n[EW], s_na[EW];
   __shared__ unsigned int s_hist[256], s_wtot[EW], s_sel[3];
   __shared__ unsigned long long s_key[PRED_K_MAX];
   __shared__ int s_ent[PRED_K_MAX];
-  // touched entities; eligible among them; those ahead of t; survivors; known tails that left untouched, and
-  // those of them below t; touched entities below t; candidates (touched + appended)
+  // touched entities; eligible among them; those ahead of the answer; survivors; known answers that left untouched,
+  // and those of them below the answer; touched entities below the answer; candidates (touched + appended)
   __shared__ int s_cnt[C_N];
   const int E = d.E, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   unsigned char *base = SMALL ? reinterpret_cast<unsigned char *>(eval_smem)
@@ -139,7 +147,8 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
 #pragma unroll 1
   for (int64_t qi = blockIdx.x; qi < a.n; qi += gridDim.x) {
     const int h = a.queries[3 * qi], r = a.queries[3 * qi + 1], t = a.queries[3 * qi + 2];
-    if (query_bad(h, r, t, E, d.R)) {
+    const int anc = HEAD ? t : h, ans = HEAD ? h : t;
+    if (query_bad(anc, r, ans, E, d.R)) {
       if (tid < a.k) {
         a.index[qi * a.k + tid] = -1;
         a.score[qi * a.k + tid] = -INFINITY;
@@ -160,16 +169,16 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
 #pragma unroll 1
     for (int jb = 0; jb < nr; jb += EW) {
       const int nw = min(EW, nr - jb);  // rules of this round
-      eval_ground_round(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
+      eval_ground_round<HEAD>(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
       eval_round_into_val<true>(l, ints, E, rb, jb, nw, s_na, val, flg, cand, &s_cnt[C_TOUCHED], wide);
     }
     if (wide) atomicOr(&a.flags[E_RANGE], 1ull);
     __syncthreads();
     const int nt = s_cnt[C_TOUCHED];
-    // the other known tails of (h, r) leave (bit 1); those no rule reached are counted for mode `all`
+    // the other known tails of (h, r) / heads of (r, t) leave (bit 1); those no rule reached are counted for `all`
     int64_t kb0 = 0, kb1 = 0;
     if (a.known_keys) {
-      const int64_t key = (int64_t)r * E + h;
+      const int64_t key = (int64_t)r * E + anc;
       int64_t lo = 0, hi = a.n_keys;
       while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
@@ -186,21 +195,21 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
     int kn = 0, knlt = 0;
     for (int64_t i = kb0 + tid; i < kb1; i += EB) {
       const int e = a.known_vals[i];
-      if ((unsigned)e >= (unsigned)E || e == t || (i > kb0 && a.known_vals[i - 1] == e)) continue;
+      if ((unsigned)e >= (unsigned)E || e == ans || (i > kb0 && a.known_vals[i - 1] == e)) continue;
       const int f = flg[e];  // one thread per distinct e: the lists are ascending within a key
       flg[e] = f | 2;
       if (!(f & 1)) {
         ++kn;
-        knlt += e < t;
+        knlt += e < ans;
       }
     }
     __syncthreads();
     // eligibility (bit 2) of the touched entities, their number and the number of those ahead of t
     bool t_ok = false;
     unsigned long long t_key = 0;
-    if (t >= 0) {
-      const double tv = val[t];
-      const int tf = flg[t];  // bits 0 and 1 are final; bit 2 is written below
+    if (ans >= 0) {
+      const double tv = val[ans];
+      const int tf = flg[ans];  // bits 0 and 1 are final; bit 2 is written below
       t_ok = (a.all || (tf & 1)) && !(tf & 2) && tv == tv;
       t_key = pred_key(tv);
     }
@@ -209,11 +218,11 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
       const int x = cand[i];
       const int f = flg[x];
       const double v = val[x];
-      tlt += x < t;
+      tlt += x < ans;
       if (!(f & 2) && v == v) {
         flg[x] = f | 4;
         ++ne;
-        if (t_ok) ahead += pred_before(pred_key(v), x, t_key, t);
+        if (t_ok) ahead += pred_before(pred_key(v), x, t_key, ans);
       }
     }
 #pragma unroll
@@ -245,7 +254,7 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
         if (zero_key > t_key)
           position += n_unt;
         else if (zero_key == t_key)
-          position += t - s_cnt[C_TOUCHED_LT] - s_cnt[C_KNOWN_LT];
+          position += ans - s_cnt[C_TOUCHED_LT] - s_cnt[C_KNOWN_LT];
       }
       // the lowest of them become candidates: whole chunks of ids until k are there (more do no harm)
       const int want = min(a.k, n_unt);
@@ -399,7 +408,7 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
   }
 }
 
-template <bool SMALL>
+template <bool SMALL, bool HEAD>
 __global__ __launch_bounds__(EB) void explain_kernel(MinerDev d, MinerLearnDev l, ExplArgs a) {
   extern __shared__ unsigned long long eval_smem[];
   __shared__ int s_n[EW], s_na[EW];
@@ -412,7 +421,7 @@ __global__ __launch_bounds__(EB) void explain_kernel(MinerDev d, MinerLearnDev l
 #pragma unroll 1
   for (int64_t qi = blockIdx.x; qi < a.n; qi += gridDim.x) {
     const int h = a.queries[3 * qi], r = a.queries[3 * qi + 1], t = a.queries[3 * qi + 2];
-    const bool bad = query_bad(h, r, t, E, d.R);
+    const bool bad = HEAD ? query_bad(t, r, h, E, d.R) : query_bad(h, r, t, E, d.R);
     const int64_t slot = qi * a.m + tid;
     int32_t *rl = a.rule + slot * a.c;  // this thread's list, if it has a slot
     long long *cl = a.count + slot * a.c;
@@ -441,7 +450,7 @@ __global__ __launch_bounds__(EB) void explain_kernel(MinerDev d, MinerLearnDev l
 #pragma unroll 1
     for (int jb = 0; jb < nr; jb += EW) {
       const int nw = min(EW, nr - jb);  // rules of this round
-      eval_ground_round(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
+      eval_ground_round<HEAD>(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
       for (int w = 0; w < nw; ++w) {  // the round's rules one after the other: list order per slot
         const int len2 = l.rule_len[rb + jb + w];
         if (len2 == 0) continue;  // an empty body reaches nothing
@@ -492,10 +501,15 @@ using namespace rnnl;
 
 extern "C" {
 
-int rnnl_miner_predict(rnnl_miner m, const int32_t *queries, int64_t n, const int64_t *known_keys,
-                       const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t k,
-                       int32_t candidates, int32_t *index, double *score, int32_t *valid, int32_t *position,
-                       uint64_t *counters, void *stream) {
+int rnnl_miner_predict_side(rnnl_miner m, int32_t side, const int32_t *queries, int64_t n, const int64_t *known_keys,
+                            const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t k,
+                            int32_t candidates, int32_t *index, double *score, int32_t *valid, int32_t *position,
+                            uint64_t *counters, void *stream) {
+  if (side != RNNL_MINER_TAIL && side != RNNL_MINER_HEAD) {
+    set_error("rnnl_miner_predict_side: side must be RNNL_MINER_TAIL or RNNL_MINER_HEAD");
+    return RNNL_ERR_INVALID;
+  }
+  const bool head = side == RNNL_MINER_HEAD;
   if (k < 1 || k > RNNL_MINER_TOPK_MAX) {
     set_error("rnnl_miner_predict: k must be 1.." + std::to_string(RNNL_MINER_TOPK_MAX));
     return RNNL_ERR_INVALID;
@@ -507,7 +521,7 @@ int rnnl_miner_predict(rnnl_miner m, const int32_t *queries, int64_t n, const in
   const bool none = !known_keys && !known_offs && !known_vals;
   const bool all = known_keys && known_offs && known_vals && n_keys >= 0;
   if (!(none || all)) {
-    set_error("rnnl_miner_predict: the known-tail arrays all or none");
+    set_error("rnnl_miner_predict: the known-answer arrays all or none");
     return RNNL_ERR_INVALID;
   }
   if (!m || !m->l.rule_off) {
@@ -540,7 +554,8 @@ int rnnl_miner_predict(rnnl_miner m, const int32_t *queries, int64_t n, const in
   const size_t E = (size_t)m->d.E;
   if (m->d.E <= EVAL_LDS_E) {
     const unsigned grid = (unsigned)std::min<int64_t>(n, EVAL_MAX_BLOCKS);
-    hipLaunchKernelGGL(predict_kernel<true>, dim3(grid), dim3(EB), (EVAL_PER_E + 5) * E, st, m->d, m->l, a);
+    auto kernel = head ? predict_kernel<true, true> : predict_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), (EVAL_PER_E + 5) * E, st, m->d, m->l, a);
   } else {
     const int rc = eval_scratch_ensure(m, "rnnl_miner_predict");
     if (rc != RNNL_OK) return rc;
@@ -557,15 +572,29 @@ int rnnl_miner_predict(rnnl_miner m, const int32_t *queries, int64_t n, const in
     a.flag_scratch = m->pred_flags;
     a.blocks = m->eval_blocks;
     const unsigned grid = (unsigned)std::min<int64_t>(n, m->eval_blocks);
-    hipLaunchKernelGGL(predict_kernel<false>, dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
+    auto kernel = head ? predict_kernel<false, true> : predict_kernel<false, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
   }
   RNNL_HIP_CHECK(hipGetLastError());
   return RNNL_OK;
 }
 
-int rnnl_miner_explain(rnnl_miner m, const int32_t *queries, int64_t n, const int32_t *index, int32_t n_slots,
-                       int32_t c, int32_t *fired, double *total, int32_t *rule, int64_t *count, uint64_t *counters,
-                       void *stream) {
+int rnnl_miner_predict(rnnl_miner m, const int32_t *queries, int64_t n, const int64_t *known_keys,
+                       const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t k,
+                       int32_t candidates, int32_t *index, double *score, int32_t *valid, int32_t *position,
+                       uint64_t *counters, void *stream) {
+  return rnnl_miner_predict_side(m, RNNL_MINER_TAIL, queries, n, known_keys, known_offs, known_vals, n_keys, k,
+                                 candidates, index, score, valid, position, counters, stream);
+}
+
+int rnnl_miner_explain_side(rnnl_miner m, int32_t side, const int32_t *queries, int64_t n, const int32_t *index,
+                            int32_t n_slots, int32_t c, int32_t *fired, double *total, int32_t *rule, int64_t *count,
+                            uint64_t *counters, void *stream) {
+  if (side != RNNL_MINER_TAIL && side != RNNL_MINER_HEAD) {
+    set_error("rnnl_miner_explain_side: side must be RNNL_MINER_TAIL or RNNL_MINER_HEAD");
+    return RNNL_ERR_INVALID;
+  }
+  const bool head = side == RNNL_MINER_HEAD;
   if (n_slots < 1 || n_slots > RNNL_MINER_TOPK_MAX) {
     set_error("rnnl_miner_explain: m (the slots per query) must be 1.." + std::to_string(RNNL_MINER_TOPK_MAX));
     return RNNL_ERR_INVALID;
@@ -599,16 +628,25 @@ int rnnl_miner_explain(rnnl_miner m, const int32_t *queries, int64_t n, const in
   const size_t E = (size_t)m->d.E;
   if (m->d.E <= EVAL_LDS_E) {
     const unsigned grid = (unsigned)std::min<int64_t>(n, EVAL_MAX_BLOCKS);
-    hipLaunchKernelGGL(explain_kernel<true>, dim3(grid), dim3(EB), EVAL_PER_E * E, st, m->d, m->l, a);
+    auto kernel = head ? explain_kernel<true, true> : explain_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), EVAL_PER_E * E, st, m->d, m->l, a);
   } else {
     const int rc = eval_scratch_ensure(m, "rnnl_miner_explain");
     if (rc != RNNL_OK) return rc;
     a.scratch = m->eval_scratch;
     const unsigned grid = (unsigned)std::min<int64_t>(n, m->eval_blocks);
-    hipLaunchKernelGGL(explain_kernel<false>, dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
+    auto kernel = head ? explain_kernel<false, true> : explain_kernel<false, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
   }
   RNNL_HIP_CHECK(hipGetLastError());
   return RNNL_OK;
+}
+
+int rnnl_miner_explain(rnnl_miner m, const int32_t *queries, int64_t n, const int32_t *index, int32_t n_slots,
+                       int32_t c, int32_t *fired, double *total, int32_t *rule, int64_t *count, uint64_t *counters,
+                       void *stream) {
+  return rnnl_miner_explain_side(m, RNNL_MINER_TAIL, queries, n, index, n_slots, c, fired, total, rule, count, counters,
+                                 stream);
 }
 
 }  // extern "C"

@@ -23,6 +23,10 @@ running mean (RuleGenerator::update) and the rule file (out_rules)
     miner.explain(queries, index, 3)    # per listed tail: fired, total, the 3 rules that contribute most, their counts
     miner.predict("test", k=10, explain=3, output="pred.tsv")   # both, as numpy arrays and as a TSV file
 
+    miner.evaluate("test", side="both") # the two-sided protocol: tail pairs then head pairs, n = 2 x triples
+    miner.predict_topk(queries, k=10, side="head")     # (h, r, t), h = -1 open: the first k heads of (?, r, t);
+    miner.scores / eval_ranks / explain / predict(..., side="head")   # every call above on the head side
+
     miner.rule_stats()                  # dict(support, body, pca_body): int64 per rule of the current lists (or of
     miner.pool_stats()                  # rel2rules given) / of the searched pool, in get_logic_rules() order
     miner.head_pairs(); miner.confidence("pca" | "std" | "head_coverage", pc=0.0)
@@ -35,6 +39,9 @@ running mean (RuleGenerator::update) and the rule file (out_rules)
     python -m rnnlogic_amd.miner -data-path D -rule-file F -evaluate test        # evaluate a rule file, no mining
     python -m rnnlogic_amd.miner -data-path D -rule-file F -predict test -predictions-file P -k 10 -explain 3
     python -m rnnlogic_amd.miner -data-path D -rule-file F -queries-file Q -predictions-file P   # head<TAB>relation[<TAB>tail]
+    python -m rnnlogic_amd.miner -data-path D -rule-file F -evaluate test -side both   # tails, heads, both: a line each
+    python -m rnnlogic_amd.miner -data-path D -rule-file F -predict test -side head -predictions-file P
+    python -m rnnlogic_amd.miner ... -side head -queries-file Q -predictions-file P    # [head]<TAB>relation<TAB>tail
 
 The pool equals the reference's for the same train graph: every relation
 path of length <= max_length from h to t of a train triple (h, r, t), the
@@ -70,7 +77,14 @@ tails by val descending, then entity id, among the entities some rule reaches
 (or all), the other known tails of (h, r) left out; and per listed tail the
 rules with a path to it, their counts and the ones that contribute most.  The
 top k are selected inside the workgroup that built val, so the (n, |E|)
-matrix of `scores` is never written.  Tail queries only.
+matrix of `scores` is never written.
+
+side="head" answers (?, r, t) with the same rules: val[e] =
+sum_k wt[k] * #paths(e -> t along body k), grounded backward from t over the
+in-edges with the triple's own edge removed, the other known heads of (r, t)
+left out.  It is bit for bit the tail side of (t, r, h) on the transposed graph
+with every body reversed.  evaluate(side="both") is the two-sided filtered
+protocol: the tail pairs of all triples, then the head pairs, as one list.
 """
 import ctypes
 import math
@@ -234,10 +248,20 @@ def _name(graph, table, i):
         return str(i)
 
 
-def read_queries_file(file_name, graph):
+def _check_side(side, what, both=False):
+    if side not in (("tail", "head", "both") if both else ("tail", "head")):
+        raise ValueError("%s: side must be 'tail'%s 'head'%s (got %r)"
+                         % (what, "," if both else " or", " or 'both'" if both else "", side))
+    return side
+
+
+def read_queries_file(file_name, graph, side="tail"):
     """Lines `head<TAB>relation` (open) or `head<TAB>relation<TAB>tail`, in the
     names of the graph's dictionaries -> (n, 3) int64 with t = -1 for the open
-    ones.  An unknown name or a malformed line is a ValueError naming the line."""
+    ones.  side 'head': `head<TAB>relation<TAB>tail`, or `<TAB>relation<TAB>tail`
+    (an empty first field) for an open query, h = -1.  An unknown name or a
+    malformed line is a ValueError naming the line."""
+    head = _check_side(side, "read_queries_file") == "head"
     out = []
     with open(file_name) as fi:
         for no, line in enumerate(fi, 1):
@@ -245,15 +269,19 @@ def read_queries_file(file_name, graph):
             if not line.strip():
                 continue
             tok = line.split("\t")
+            if head and len(tok) != 3:
+                raise ValueError("%s:%d: expected head<TAB>relation<TAB>tail or <TAB>relation<TAB>tail (head queries)"
+                                 % (file_name, no))
             if len(tok) not in (2, 3):
                 raise ValueError("%s:%d: expected head<TAB>relation or head<TAB>relation<TAB>tail" % (file_name, no))
-            if tok[0] not in graph.entity2id:
+            open_head = head and tok[0] == ""
+            if not open_head and tok[0] not in graph.entity2id:
                 raise ValueError("%s:%d: unknown entity %r" % (file_name, no, tok[0]))
             if tok[1] not in graph.relation2id:
                 raise ValueError("%s:%d: unknown relation %r" % (file_name, no, tok[1]))
             if len(tok) == 3 and tok[2] not in graph.entity2id:
                 raise ValueError("%s:%d: unknown entity %r" % (file_name, no, tok[2]))
-            out.append((graph.entity2id[tok[0]], graph.relation2id[tok[1]],
+            out.append((-1 if open_head else graph.entity2id[tok[0]], graph.relation2id[tok[1]],
                         graph.entity2id[tok[2]] if len(tok) == 3 else -1))
     return np.asarray(out, dtype=np.int64).reshape(-1, 3)
 
@@ -348,6 +376,7 @@ class RuleMiner(object):
         self.chunk_triples = None     # triples per grounding chunk; None: as many as budget_bytes allows
         self.budget_bytes = 1 << 30   # device memory for one chunk's (triple, rule, destination, count) entries
         self._known = None            # known tails over train + valid + test (eval_ranks), built once
+        self._known_h = None          # known heads, the same
         self._rule_len = np.zeros(0, dtype=np.int32)       # the current rule lists, as _set_rule_arrays got them
         self._rule_body = np.zeros((0, 3), dtype=np.int32)
         self._pool_stats = None       # pool_stats() of the searched pool, until the next search
@@ -721,26 +750,39 @@ class RuleMiner(object):
             raise ValueError("query triple out of range")
         return q.astype(np.int32)
 
+    def _known_lists(self, mode):
+        from .data import _DeviceLists
+        from .kge import true_answers
+        every = [np.asarray(getattr(self.graph, name, None) or [], dtype=np.int64).reshape(-1, 3)
+                 for name in ("train_facts", "valid_facts", "test_facts")]
+        return _DeviceLists(true_answers(np.concatenate(every), self.graph.entity_size, mode), self.device)
+
     def _known_tails(self):
         if self._known is None:
-            from .data import _DeviceLists
-            from .kge import true_answers
-            every = [np.asarray(getattr(self.graph, name, None) or [], dtype=np.int64).reshape(-1, 3)
-                     for name in ("train_facts", "valid_facts", "test_facts")]
-            self._known = _DeviceLists(true_answers(np.concatenate(every), self.graph.entity_size, "tail"),
-                                       self.device)
+            self._known = self._known_lists("tail")
         return self._known
 
+    def _known_heads(self):
+        """Keys r |E| + t -> the known heads over train, valid and test, built once."""
+        if self._known_h is None:
+            self._known_h = self._known_lists("head")
+        return self._known_h
+
+    def _known_side(self, side):
+        return self._known_heads() if side == "head" else self._known_tails()
+
     @torch.no_grad()
-    def _evaluate(self, triples, filtered, want_val):
+    def _evaluate(self, triples, filtered, want_val, side="tail"):
+        _check_side(side, "RuleMiner")
         q = self._queries(triples)
         n, E = len(q), self.graph.entity_size
         with torch.cuda.device(self.device):
             qd = torch.from_numpy(q).to(self.device)
             ranks = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
             val = torch.zeros((n, E), dtype=torch.float64, device=self.device) if want_val else None
-            k = self._known_tails() if filtered else None
-            _native.call("rnnl_miner_evaluate", self._handle, qd.data_ptr(), n,
+            k = self._known_side(side) if filtered else None
+            _native.call("rnnl_miner_evaluate_side", self._handle,
+                         _native.MINER_HEAD if side == "head" else _native.MINER_TAIL, qd.data_ptr(), n,
                          k.keys.data_ptr() if k else None, k.offs.data_ptr() if k else None,
                          k.vals.data_ptr() if k else None, k.keys.numel() if k else 0, ranks.data_ptr(),
                          val.data_ptr() if want_val else None, self._counters.data_ptr(),
@@ -748,35 +790,52 @@ class RuleMiner(object):
             self._check_counters()
         return ranks, val
 
-    def scores(self, triples):
+    def scores(self, triples, side="tail"):
         """(n, |E|) float64 on the device: per query (h, r, t) the val of every
         entity — sum over r's rules of weight * path count from h, the triple's
-        own edge removed — bitwise what the reference computes."""
-        return self._evaluate(triples, False, True)[1]
+        own edge removed — bitwise what the reference computes.  side 'head':
+        weight * path count from the entity to t, the same edge removed."""
+        return self._evaluate(triples, False, True, side)[1]
 
-    def eval_ranks(self, triples, filtered=True):
+    def eval_ranks(self, triples, filtered=True, side="tail"):
         """(n, 2) numpy int64: per query (num_g, num_ge), the entities scoring
         above the true tail / at least as high (the tail included).  filtered:
         the other known tails of (h, r) over train, valid and test are left
-        out (a graph without valid_facts / test_facts filters by train)."""
-        return self._evaluate(triples, filtered, False)[0].cpu().numpy().astype(np.int64)
+        out (a graph without valid_facts / test_facts filters by train).  side
+        'head': the same of the true head among the heads of (?, r, t), the
+        other known heads of (r, t) left out."""
+        return self._evaluate(triples, filtered, False, side)[0].cpu().numpy().astype(np.int64)
 
-    def evaluate(self, split="test", triples=None, filtered=True):
+    def evaluate(self, split="test", triples=None, filtered=True, side="tail"):
         """ReasoningPredictor::evaluate over graph.valid_facts / test_facts
         (split 'valid' / 'test') or the given triples, with the current rules
-        and weights: dict(mr, mrr, hit1, hit3, hit10, n)."""
+        and weights: dict(mr, mrr, hit1, hit3, hit10, n).  side 'head': the
+        head side of every triple; 'both': the tail pairs of all triples, then
+        the head pairs, as one list — n is twice the triple count."""
+        _check_side(side, "evaluate", both=True)
         if triples is None:
             if split not in ("valid", "test"):
                 raise ValueError("evaluate: split must be 'valid' or 'test'")
             triples = getattr(self.graph, split + "_facts")
-        return expectation_metrics(self.eval_ranks(triples, filtered), self.graph.entity_size)
+        pairs = [self.eval_ranks(triples, filtered, s) for s in (("tail", "head") if side == "both" else (side,))]
+        return expectation_metrics(np.concatenate(pairs), self.graph.entity_size)
 
     # ----------------------------------------------------------- predictions
-    def _pred_queries(self, queries):
-        """(n, 2) (h, r) or (n, 3) (h, r, t) with t >= 0 or -1 -> (n, 3) int32, open queries with t = -1."""
+    def _pred_queries(self, queries, side="tail"):
+        """(n, 2) (h, r) or (n, 3) (h, r, t) with t >= 0 or -1 -> (n, 3) int32, open queries with t = -1.
+        side 'head': (n, 3) (h, r, t) with h >= 0 or -1, the open ones."""
         q = np.asarray(queries, dtype=np.int64)
         if q.size == 0:
             q = q.reshape(0, 3)
+        if _check_side(side, "RuleMiner") == "head":
+            if q.ndim != 2 or q.shape[1] != 3:
+                raise ValueError("head-side queries must be (n, 3) (h, r, t), h = -1: an open query (got shape %r)"
+                                 % (q.shape,))
+            E, R = self.graph.entity_size, self.graph.relation_size
+            if len(q) and (q[:, 1:].min() < 0 or q[:, 2].max() >= E or q[:, 1].max() >= R or q[:, 0].min() < -1
+                           or q[:, 0].max() >= E):
+                raise ValueError("query out of range (h, t in [0, %d), r in [0, %d); h = -1: an open query)" % (E, R))
+            return np.ascontiguousarray(q, dtype=np.int32)
         if q.ndim != 2 or q.shape[1] not in (2, 3):
             raise ValueError("queries must be (n, 2) (h, r) or (n, 3) (h, r, t) (got shape %r)" % (q.shape,))
         if q.shape[1] == 2:
@@ -788,7 +847,7 @@ class RuleMiner(object):
         return np.ascontiguousarray(q, dtype=np.int32)
 
     @torch.no_grad()
-    def predict_topk(self, queries, k=10, filtered=True, candidates="reached"):
+    def predict_topk(self, queries, k=10, filtered=True, candidates="reached", side="tail"):
         """The first k tails of each query by the score of `scores` (val
         descending, then entity id; rnnl_miner_predict, csrc/mine_predict.hip),
         without the (n, |E|) matrix.  queries: (n, 2) (h, r) — open: no edge is
@@ -800,13 +859,15 @@ class RuleMiner(object):
         (bitwise `scores`; -inf past valid), valid (n,) int32 = min(k,
         #eligible), position (n,) int32 = the 0-based place of t in the whole
         eligible order (also past k), -1 if t is not eligible or the query is
-        open."""
+        open.  side 'head': the first k heads of (?, r, t) by the head-side
+        score; queries (n, 3) (h, r, t), h = -1 open; the other known heads of
+        (r, t) leave, h stays; position is the place of h."""
         k = int(k)
         if not 1 <= k <= _native.MINER_TOPK_MAX:
             raise ValueError("predict_topk: k must be 1..%d (got %d)" % (_native.MINER_TOPK_MAX, k))
         if candidates not in ("reached", "all"):
             raise ValueError("predict_topk: candidates must be 'reached' or 'all' (got %r)" % (candidates,))
-        q = self._pred_queries(queries)
+        q = self._pred_queries(queries, side)
         n = len(q)
         with torch.cuda.device(self.device):
             qd = torch.from_numpy(q).to(self.device)
@@ -814,8 +875,9 @@ class RuleMiner(object):
             score = torch.empty((n, k), dtype=torch.float64, device=self.device)
             valid = torch.empty(n, dtype=torch.int32, device=self.device)
             position = torch.empty(n, dtype=torch.int32, device=self.device)
-            kn = self._known_tails() if filtered else None
-            _native.call("rnnl_miner_predict", self._handle, qd.data_ptr(), n,
+            kn = self._known_side(side) if filtered else None
+            _native.call("rnnl_miner_predict_side", self._handle,
+                         _native.MINER_HEAD if side == "head" else _native.MINER_TAIL, qd.data_ptr(), n,
                          kn.keys.data_ptr() if kn else None, kn.offs.data_ptr() if kn else None,
                          kn.vals.data_ptr() if kn else None, kn.keys.numel() if kn else 0, k,
                          _native.MINER_ALL if candidates == "all" else _native.MINER_REACHED, index.data_ptr(),
@@ -825,7 +887,7 @@ class RuleMiner(object):
         return index, score, valid, position
 
     @torch.no_grad()
-    def explain(self, queries, index, rules_per_tail=3):
+    def explain(self, queries, index, rules_per_tail=3, side="tail"):
         """The rules behind the entities index (n, m) int32 (-1: an unused
         slot; m <= 256) of each query (rnnl_miner_explain).  Returns device
         tensors: fired (n, m) int32 = the rules with a path to the entity,
@@ -833,11 +895,12 @@ class RuleMiner(object):
         (bitwise the entity's score), rule (n, m, c) int32 = the c =
         rules_per_tail (1..16) rules with the largest weight * count, ties by
         list index, as indices into the relation's rule list (-1 unused), and
-        count (n, m, c) int64 = their path counts."""
+        count (n, m, c) int64 = their path counts.  side 'head': the entities
+        are heads of (?, r, t), the paths run from the entity to t."""
         c = int(rules_per_tail)
         if not 1 <= c <= _native.MINER_EXPLAIN_MAX:
             raise ValueError("explain: rules_per_tail must be 1..%d (got %d)" % (_native.MINER_EXPLAIN_MAX, c))
-        q = self._pred_queries(queries)
+        q = self._pred_queries(queries, side)
         n = len(q)
         with torch.cuda.device(self.device):
             idx = torch.as_tensor(index, device=self.device).to(torch.int32).contiguous()
@@ -850,14 +913,15 @@ class RuleMiner(object):
             total = torch.empty((n, m), dtype=torch.float64, device=self.device)
             rule = torch.empty((n, m, c), dtype=torch.int32, device=self.device)
             count = torch.empty((n, m, c), dtype=torch.int64, device=self.device)
-            _native.call("rnnl_miner_explain", self._handle, qd.data_ptr(), n, idx.data_ptr(), m, c,
-                         fired.data_ptr(), total.data_ptr(), rule.data_ptr(), count.data_ptr(),
+            _native.call("rnnl_miner_explain_side", self._handle,
+                         _native.MINER_HEAD if side == "head" else _native.MINER_TAIL, qd.data_ptr(), n,
+                         idx.data_ptr(), m, c, fired.data_ptr(), total.data_ptr(), rule.data_ptr(), count.data_ptr(),
                          self._counters.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
             self._check_counters()
         return fired, total, rule, count
 
     def predict(self, split="test", triples=None, k=10, filtered=True, explain=0, rules_per_tail=3,
-                candidates="reached", output=None):
+                candidates="reached", output=None, side="tail"):
         """The miner's answers on graph.valid_facts / test_facts (split
         'valid' / 'test') or the given queries ((n, 2) or (n, 3), as
         predict_topk), with the current rules and weights.  Returns a dict of
@@ -867,13 +931,17 @@ class RuleMiner(object):
         min(m, k) places (`explain`).  output: one TSV line per prediction —
         head, relation, place (1-based), tail, repr(score), `*` on the known
         answer, then for the explained places `head <- b1, b2:count:weight`
-        per listed rule, names from the graph's dictionaries."""
+        per listed rule, names from the graph's dictionaries.  side 'head':
+        the heads of (?, r, t); the lines keep the triple's orientation —
+        predicted head, relation, place written h1, h2, ..., the query's tail,
+        score, `*`, rules."""
+        _check_side(side, "predict")
         if triples is None:
             if split not in ("valid", "test"):
                 raise ValueError("predict: split must be 'valid' or 'test'")
             triples = getattr(self.graph, split + "_facts")
-        q = self._pred_queries(triples)
-        index, score, valid, position = self.predict_topk(q, k, filtered, candidates)
+        q = self._pred_queries(triples, side)
+        index, score, valid, position = self.predict_topk(q, k, filtered, candidates, side)
         out = dict(h=q[:, 0].astype(np.int64), r=q[:, 1].astype(np.int64), t=q[:, 2].astype(np.int64),
                    index=index.cpu().numpy(), score=score.cpu().numpy(), valid=valid.cpu().numpy(),
                    position=position.cpu().numpy())
@@ -881,14 +949,14 @@ class RuleMiner(object):
         if m > 0:
             names = ("explain_fired", "explain_total", "explain_rule", "explain_count")
             if len(q):
-                got = self.explain(q, index[:, :m].contiguous(), rules_per_tail)
+                got = self.explain(q, index[:, :m].contiguous(), rules_per_tail, side)
                 out.update((name, v.cpu().numpy()) for name, v in zip(names, got))
             else:
                 c = int(rules_per_tail)
                 out.update(zip(names, (np.zeros((0, m), np.int32), np.zeros((0, m), np.float64),
                                        np.zeros((0, m, c), np.int32), np.zeros((0, m, c), np.int64))))
         if output is not None:
-            self._write_predictions(output, out, m)
+            self._write_predictions(output, out, m, side)
         return out
 
     def rule_text(self, r, k, count=None, weight=None):
@@ -899,15 +967,17 @@ class RuleMiner(object):
                              ", ".join(_name(self.graph, "id2relation", b) for b in body))
         return text if count is None else "%s:%d:%r" % (text, count, float(weight))
 
-    def _write_predictions(self, path, out, m):
+    def _write_predictions(self, path, out, m, side="tail"):
         wt = self.weights() if m > 0 else None
+        head = side == "head"
         with open(path, "w") as fo:
             for i in range(len(out["h"])):
                 h, r, t = int(out["h"][i]), int(out["r"][i]), int(out["t"][i])
                 for j in range(int(out["valid"][i])):
                     e = int(out["index"][i, j])
-                    cols = [_name(self.graph, "id2entity", h), _name(self.graph, "id2relation", r), str(j + 1),
-                            _name(self.graph, "id2entity", e), repr(float(out["score"][i, j])), "*" if e == t else ""]
+                    cols = [_name(self.graph, "id2entity", e if head else h), _name(self.graph, "id2relation", r),
+                            "h%d" % (j + 1) if head else str(j + 1), _name(self.graph, "id2entity", t if head else e),
+                            repr(float(out["score"][i, j])), "*" if e == (h if head else t) else ""]
                     if j < m:
                         cols += [self.rule_text(r, kk, c, wt[r][kk]) for kk, c in
                                  zip(out["explain_rule"][i, j].tolist(), out["explain_count"][i, j].tolist())
@@ -1081,6 +1151,7 @@ def main(argv=None):
     ap.add_argument("-explain", dest="explain", type=int, default=0)
     ap.add_argument("-rules-per-tail", dest="rules_per_tail", type=int, default=3)
     ap.add_argument("-candidates", dest="candidates", choices=["reached", "all"], default="reached")
+    ap.add_argument("-side", dest="side", choices=["tail", "head", "both"], default="tail")
     a = ap.parse_args(argv)
     predicting = a.predict is not None or a.queries_file is not None
     if a.output_file is None and a.rule_file is None:
@@ -1092,6 +1163,8 @@ def main(argv=None):
         ap.error("-predict takes a split, -queries-file a file of queries: give one of them")
     if predicting != (a.predictions_file is not None):
         ap.error("-predict / -queries-file write their answers to -predictions-file: give both or neither")
+    if predicting and a.side == "both":
+        ap.error("-side both belongs to -evaluate: -predict / -queries-file answer one side, tail or head")
     if predicting and not 1 <= a.k <= _native.MINER_TOPK_MAX:
         ap.error("-k must be 1..%d" % _native.MINER_TOPK_MAX)
     if predicting and (a.explain < 0 or not 1 <= a.rules_per_tail <= _native.MINER_EXPLAIN_MAX):
@@ -1106,7 +1179,7 @@ def main(argv=None):
     miner = RuleMiner(KnowledgeGraph(a.data_path),
                       max_body=MAX_BODY if a.rule_file is not None else max(3, a.max_length))
     # (a name the dictionaries do not know stops the run before it mines)
-    queries = read_queries_file(a.queries_file, miner.graph) if a.queries_file is not None else None
+    queries = read_queries_file(a.queries_file, miner.graph, a.side) if a.queries_file is not None else None
     if a.output_file is not None:
         miner.mine(a.max_length, a.iterations, a.top_n, a.top_k, a.lr, a.wd, a.temp, a.top_n_out, seed=a.seed,
                    prior=a.prior, prior_weight=a.prior_weight, pc=a.pc)
@@ -1119,10 +1192,15 @@ def main(argv=None):
         if a.stats_file is not None:
             print("#Rule statistics written: %d" % miner.write_list_stats(a.stats_file, a.pc))
     for split in {None: (), "both": ("valid", "test")}.get(a.evaluate, (a.evaluate,)):
-        print(metrics_line(split.capitalize(), miner.evaluate(split)))
+        if a.side == "tail":
+            print(metrics_line(split.capitalize(), miner.evaluate(split)))
+            continue
+        for side in (("tail", "head", "both") if a.side == "both" else (a.side,)):
+            print(metrics_line("%s (%s)" % (split.capitalize(), side if side == "both" else side + "s"),
+                               miner.evaluate(split, side=side)))
     if predicting:
         out = miner.predict(a.predict, queries, a.k, True, a.explain, a.rules_per_tail, a.candidates,
-                            a.predictions_file)
+                            a.predictions_file, a.side)
         print("#Predictions written: %d" % int(np.sum(out["valid"])))
 
 
