@@ -336,8 +336,12 @@ __global__ __launch_bounds__(BWB) void sum_backward_kernel(KParams p, const floa
         float h = relb[2 * lane + j];
 #pragma unroll
         for (int i = 0; i < 16; ++i) h = fmaf(w0r[j][i], zc[i], h);
+        // dL/dW1[o] = sum_c g_c relu(h_co), a product: an inactive unit adds
+        // g x 0 — nothing for a finite g, NaN for a non-finite one, as the
+        // reference's matmul does (the other sums go through ReLU's backward,
+        // a selection, and skip the unit)
+        a_w1[j] = fmaf(gc, relu_f(h), a_w1[j]);
         if (h > 0.f) {
-          a_w1[j] = fmaf(gc, h, a_w1[j]);
           const float gh = gc * S.w1[2 * lane + j];
           a_b0[j] += gh;
           run_s[j] += gh;
