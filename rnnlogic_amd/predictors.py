@@ -18,7 +18,6 @@ the exported grounding COO.
 
 There is no CPU fallback: on a CPU tensor forward() raises.
 """
-import collections
 import ctypes
 import logging
 import math
@@ -31,6 +30,7 @@ from . import _native
 from .data import _DeviceHandle
 from .embedding import RotatE
 from .layers import MLP, FuncToNode, FuncToNodeSum
+from .lookahead import Grounded, Lookahead
 
 
 def _read_rules(input):
@@ -85,7 +85,14 @@ class _HipGrounding(object):
     """Grounding plumbing shared by Predictor and PredictorPlus: the per-device
     rules handle (prefix tries), the forward workspace with its overflow retry,
     and the grounding COO export.  Needs self.graph, self.rules,
-    self._native_rules, self._ws and self.capacity_scale."""
+    self._native_rules, self._ws and self.capacity_scale; the training
+    lookahead (prefetch) also self._lookahead = {} (per device: Lookahead)."""
+
+    # groundings launched ahead of the training step that needs them
+    # (TrainerPredictor.train; 0 turns the lookahead off)
+    prefetch_depth = 2
+    prefetch_dropped = 0  # queued groundings discarded (rows not the queue's head)
+    prefetch_hits = 0  # forwards that scored a grounding made ahead
 
     def _device_index(self, device):
         return device.index if device.index is not None else torch.cuda.current_device()
@@ -290,33 +297,24 @@ class _HipGrounding(object):
         if nq == 0:
             return
         key = self._device_index(device)
-        pf = self._pf.get(key)
-        if pf is None:
-            pf = self._pf[key] = {"stream": torch.cuda.Stream(device), "ring": {}, "next": 0,
-                                  "queue": collections.deque()}
-        if len(pf["queue"]) >= self.prefetch_depth:
+        la = self._lookahead.get(key)
+        if la is None:
+            la = self._lookahead[key] = Lookahead(self, device)
+        if len(la.entries) >= self.prefetch_depth:
             return
         g, nr = self.graph.device_graph(device), self.native_rules(device)
         scale = self.capacity_scale
         need = ctypes.c_size_t()
         _native.call("rnnl_forward_workspace_size", g, nr.ptr, nq, scale, ctypes.byref(need))
-        # ring of depth + 1 workspaces: the forward in flight keeps one until its backward
-        slot = pf["next"] % (self.prefetch_depth + 1)
-        pf["next"] += 1
-        ws = pf["ring"].get(slot)
-        if ws is None or ws.numel() < need.value:
-            ws = pf["ring"][slot] = torch.empty(need.value, dtype=torch.uint8, device=device)
+        ws, hdr, ev = la.slot(need.value, device)
         n_cand = torch.empty(nq, dtype=torch.int32, device=device)
-        side, main = pf["stream"], torch.cuda.current_stream(device)
+        side, main = la.stream, torch.cuda.current_stream(device)
         # inputs, and the slot's previous user (its backward is on the current stream already)
         side.wait_stream(main)
         self._prefetch_ground(g, nr, h, r, etr, nq, n_cand, ws, scale, side.cuda_stream)
         # the grounding's status / totals and the one-relation flag, copied to the
         # host behind it: the forward reads them without waiting for the current stream
-        # (pinned buffer and event of the ring slot: the slot's previous entry was
-        # consumed, or dropped behind the same side stream, before it comes round)
-        hdr, ev = self._host_slot(pf, "pf", slot, self.prefetch_depth + 1)
-        hb = self._header_bytes()
+        hb = la.header_bytes
         with torch.cuda.stream(side):
             hdr[:hb].copy_(ws[:hb], non_blocking=True)  # status, totals and the one-relation flag
             hdr[hb:hb + 8].copy_(r[:1].view(torch.uint8), non_blocking=True)  # the first row's relation
@@ -326,24 +324,7 @@ class _HipGrounding(object):
         for t in (ws, n_cand, h, r) + ((etr,) if etr is not None else ()):
             t.record_stream(side)
         self._ws_touch(ws)
-        pf["queue"].append((all_h, all_r, edges_to_remove, ws, scale, n_cand, ev, (h, r, etr), hdr))
-
-    def _host_slot(self, pf, name, k, n):
-        """(pinned header buffer, event) number k % n of a ring kept in pf:
-        reused instead of a pinned allocation and an event creation per step."""
-        ring = pf.get(name)
-        if ring is None or len(ring) != n:
-            hb = self._header_bytes() + 8  # + the first row's relation (int64)
-            ring = pf[name] = [(torch.empty(hb, dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
-                               for _ in range(n)]
-        return ring[k % n]
-
-    def _header_bytes(self):
-        if getattr(self, "_hdr_bytes", None) is None:
-            n = ctypes.c_size_t()
-            _native.call("rnnl_forward_header_bytes", ctypes.byref(n))
-            self._hdr_bytes = n.value
-        return self._hdr_bytes
+        la.entries.append(Grounded((all_h, all_r, edges_to_remove), ws, scale, n_cand, ev, (h, r, etr), hdr))
 
     def check_deferred(self, keep=0):
         """Raise the scoring pass's own error (an integer range flag) of the
@@ -354,68 +335,51 @@ class _HipGrounding(object):
         those forwards have then already run their backward and optimizer
         step on the flagged scores: the error names the forward, and a run
         resumed from a checkpoint written after it should not trust it."""
-        q = getattr(self, "_deferred_status", None)
-        while q and len(q) > keep:
-            dh, ev, n = q.popleft()
-            ev.synchronize()
-            rc = _native.lib().rnnl_forward_status_host(dh.data_ptr(), None)
-            if rc != _native.RNNL_OK:
-                q.clear()
-                raise _native.NativeError(rc, "%s (scoring pass of lookahead forward #%d, read late: that step's "
-                                              "backward and optimizer update have already been applied)" % (
-                                                  _native.lib().rnnl_last_error().decode(errors="replace"), n))
+        for la in self._lookahead.values():
+            la.check_deferred(keep)
 
-    def _prefetched(self, device, all_h, all_r, edges_to_remove, peek=False):
-        """The queued grounding of exactly these row tensors, or None.  Entries
-        grounded at another capacity_scale (a retry raised it since) and those
-        queued before the match (batches that ran without their lookahead) are
-        dropped; entries after it are later batches and stay queued.
-        peek: leave the match queued."""
-        pf = self._pf.get(self._device_index(device))
-        if not pf or not pf["queue"]:
+    def drop_lookahead(self):
+        """Discard (and count as dropped) every grounding still queued: a new
+        loop's batches are new tensor objects, which the leftovers never match."""
+        for la in self._lookahead.values():
+            la.retain([])
+
+    def _discard_lookahead(self):
+        """set_rules: queued groundings and their workspaces belong to the old rules."""
+        for la in self._lookahead.values():
+            la.reset()
+
+    def _prefetched(self, device, rows, peek=False):
+        """The queued grounding (Grounded) of exactly these row objects (all_h,
+        all_r, edges_to_remove) at the current capacity_scale, or None
+        (LookaheadQueue.take)."""
+        la = self._lookahead.get(self._device_index(device))
+        return la.take(rows, self.capacity_scale, peek) if la else None
+
+    def _score_grounded_ahead(self, device, pre, totals, fill, score, accept=None, single_relation=False):
+        """The scoring half of a forward on the grounding `pre` made ahead
+        (prefetch).  fill() writes the base score rows, score(ws, scale,
+        n_cand) launches the scoring pass; accept() (nullable), called behind
+        that launch, may still refuse its result.  Returns pre's (ws, scale,
+        n_cand), or None where the caller takes the one-call path and its
+        retry: the grounding overflowed (or failed otherwise), or accept()
+        refused.  `totals` and self._flags are read from pre's header copy."""
+        pre.event.synchronize()  # that grounding and its header copy, not the later side-stream work
+        rc = _native.lib().rnnl_forward_status_host(pre.header.data_ptr(), totals.ctypes.data_as(ctypes.c_void_p))
+        _native.call("rnnl_forward_flags_host", pre.header.data_ptr(), self._flags.ctypes.data_as(ctypes.c_void_p))
+        if single_relation:
+            self._check_one_relation()
+        if rc != _native.RNNL_OK:
             return None
-        q = pf["queue"]
-        stale = [e for e in q if e[4] != self.capacity_scale]
-        if stale:
-            self._drop_lookahead(pf, [e for e in q if e[4] == self.capacity_scale], len(stale))
-            q = pf["queue"]
-        for i, e in enumerate(q):
-            if e[0] is all_h and e[1] is all_r and e[2] is edges_to_remove:
-                if i:
-                    self._drop_lookahead(pf, list(q)[i:], i)
-                    q = pf["queue"]
-                if peek:
-                    return q[0]
-                self.prefetch_hits = getattr(self, "prefetch_hits", 0) + 1
-                return q.popleft()
-        return None  # these rows were not grounded ahead; the queued ones are later batches
-
-    def _drop_lookahead(self, pf, keep, n):
-        # the side stream's work on dropped entries still ends before their
-        # ring slots come round again (record_stream, the slots' order)
-        self.prefetch_dropped += n
-        logging.debug(type(self).__name__ + ": %d lookahead groundings dropped (%d so far)", n, self.prefetch_dropped)
-        pf["queue"] = collections.deque(keep)
-
-    def _defer_status(self, device, ws):
-        """After a scoring pass on a prefetched grounding: its header copied
-        behind it into a pinned ring slot, checked two forwards later
-        (check_deferred) instead of waiting for the pass now."""
-        hb = self._header_bytes()
-        main = torch.cuda.current_stream(device)
-        self._lookahead_forwards = getattr(self, "_lookahead_forwards", 0) + 1
-        dh, dev_ev = self._host_slot(self._pf[self._device_index(device)], "dev", self._lookahead_forwards, 4)
-        dh[:hb].copy_(ws[:hb], non_blocking=True)
-        dev_ev.record(main)
-        if getattr(self, "_deferred_status", None) is None:
-            self._deferred_status = collections.deque()
-        self._deferred_status.append((dh, dev_ev, self._lookahead_forwards))
-
-    @staticmethod
-    def _prefetch_relation(hdr, hb):
-        """The first row's relation recorded by prefetch (host read of the
-        pinned slot; its event has been waited on)."""
-        return int(hdr[hb:hb + 8].view(torch.int64)[0])
+        fill()
+        torch.cuda.current_stream(device).wait_event(pre.event)
+        score(pre.ws, pre.scale, pre.n_cand)
+        if accept is not None and not accept():
+            return None
+        # the scoring pass's own range flag: copied behind it, read two forwards
+        # later (a ring of 4 pinned buffers / events: at most 2 are pending)
+        self._lookahead[self._device_index(device)].defer(pre.ws)
+        return pre.ws, pre.scale, pre.n_cand
 
     def _reference_nonfinite(self, device, all_r, ridx, rule_vals, row, ce, node, C):
         """Where the reference's dense sums over a relation's rules meet 0 x
@@ -682,11 +646,7 @@ class Predictor(_HipGrounding, torch.nn.Module):
         self._roots = {}
         self._ws_uses = {}  # per workspace pointer: launches onto it so far
         self._flags = np.zeros(1, dtype=np.uint32)  # the last launch's header flags (_status)
-        self._pf = {}  # per device: training lookahead (prefetch): side stream, workspace ring, queue
-        # groundings launched ahead of the training step that needs them
-        # (TrainerPredictor.train; 0 turns the lookahead off)
-        self.prefetch_depth = 2
-        self.prefetch_dropped = 0  # queued groundings discarded (rows not the queue's head)
+        self._lookahead = {}
         self.capacity_scale = 1
 
     def set_rules(self, input):
@@ -701,7 +661,7 @@ class Predictor(_HipGrounding, torch.nn.Module):
         self._native_rules = {}
         self._lin_cache = {}
         self._roots = {}
-        self._pf = {}  # queued lookahead groundings belong to the old rules
+        self._discard_lookahead()
 
     # ------------------------------------------------------------------ native plumbing
     def node_weights(self, device):
@@ -778,7 +738,7 @@ class Predictor(_HipGrounding, torch.nn.Module):
                     torch.empty((0, E), dtype=torch.bool, device=device),
                     torch.empty(0, dtype=torch.int32, device=device), None, None, 0)
         self.check_deferred(keep=1)
-        pre = self._prefetched(device, *raw)
+        pre = self._prefetched(device, raw)
         g, nr = self.graph.device_graph(device), self.native_rules(device)
         node_w = self.node_weights(device)
         stream = torch.cuda.current_stream(device).cuda_stream
@@ -802,28 +762,18 @@ class Predictor(_HipGrounding, torch.nn.Module):
                          all_r.data_ptr(), etr.data_ptr() if etr is not None else None, nq, score.data_ptr(),
                          mask8.data_ptr() if mask8 is not None else None, n_cand.data_ptr(), ws.data_ptr(),
                          ws.numel(), scale, stream)
+
+        def score_ahead(ws, scale, n_cand):
+            _native.call("rnnl_predictor_score", g, nr.ptr, node_w.data_ptr(), feature, all_h.data_ptr(),
+                         all_r.data_ptr(), nq, score.data_ptr(), mask8.data_ptr() if mask8 is not None else None,
+                         n_cand.data_ptr(), ws.data_ptr(), ws.numel(), scale, stream)
         totals = np.zeros(2, dtype=np.int64)  # (candidates, bucket entries), read with the status
-        if pre is not None:  # grounded ahead (prefetch): the scoring half only
-            _, _, _, ws, scale, n_cand_pf, ev, _, hdr = pre
-            ev.synchronize()  # that grounding and its header copy, not the later side-stream work
-            rc = _native.lib().rnnl_forward_status_host(hdr.data_ptr(), totals.ctypes.data_as(ctypes.c_void_p))
-            _native.call("rnnl_forward_flags_host", hdr.data_ptr(), self._flags.ctypes.data_as(ctypes.c_void_p))
-            if single_relation:
-                self._check_one_relation()
-            if rc == _native.RNNL_OK:
-                fill()
-                main = torch.cuda.current_stream(device)
-                main.wait_event(ev)
-                _native.call("rnnl_predictor_score", g, nr.ptr, node_w.data_ptr(), feature, all_h.data_ptr(),
-                             all_r.data_ptr(), nq, score.data_ptr(), mask8.data_ptr() if mask8 is not None else None,
-                             n_cand_pf.data_ptr(), ws.data_ptr(), ws.numel(), scale, stream)
-                # the scoring pass's range flag: copied behind it, read two forwards
-                # later (a ring of 4 pinned buffers / events: at most 2 are pending)
-                self._defer_status(device, ws)
-                n_cand = n_cand_pf
-            else:  # overflow (or another failure): the one-call path, with its retry
-                pre = None
-        if pre is None:
+        # grounded ahead (prefetch): the scoring half only
+        used = pre is not None and self._score_grounded_ahead(device, pre, totals, fill, score_ahead,
+                                                              single_relation=single_relation)
+        if used:
+            ws, scale, n_cand = used
+        else:
             ws, scale = self._launch(device, nq, run, totals)
             if single_relation:
                 self._check_one_relation()
@@ -1006,6 +956,22 @@ class Predictor(_HipGrounding, torch.nn.Module):
         return H
 
 
+def _train_node_records(nr, agg, head, emb, add_w, stream):
+    """The per-trie-node records of a training forward (rnnl_node_weights*)
+    from the embedding table `emb` (num_rules x 16 f32 on the device) and, for
+    AGG_SUM, FuncToNodeSum's Linear weight `add_w`: a new byte tensor.
+    head >= 0: a one-relation batch reads that head's trie only."""
+    nbytes = ctypes.c_size_t()
+    _native.call("rnnl_node_weights_size", nr.ptr, agg, ctypes.byref(nbytes))
+    node_w = torch.empty(nbytes.value, dtype=torch.uint8, device=emb.device)
+    add_w = add_w.data_ptr() if add_w is not None else None
+    if head >= 0:
+        _native.call("rnnl_node_weights_head", nr.ptr, head, emb.data_ptr(), 16, agg, add_w, node_w.data_ptr(), stream)
+    else:
+        _native.call("rnnl_node_weights", nr.ptr, emb.data_ptr(), 16, agg, add_w, node_w.data_ptr(), stream)
+    return node_w
+
+
 class _PlusSumTrain(torch.autograd.Function):
     """PredictorPlus.forward under autograd for the SUM aggregator (hidden 16):
     the fused HIP forward (rnnl_predictorplus_forward with the batch's edge
@@ -1031,16 +997,8 @@ class _PlusSumTrain(torch.autograd.Function):
         g, nr = model.graph.device_graph(device), model.native_rules(device)
         emb_d = emb.detach().float().contiguous()
         ws_ = [t.detach().float().contiguous() for t in (add_w, add_b, ln_w, ln_b, s0_w, s0_b, s1_w, s1_b, rel_w)]
-        nbytes = ctypes.c_size_t()
-        _native.call("rnnl_node_weights_size", nr.ptr, _native.AGG_SUM, ctypes.byref(nbytes))
-        node_w = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
         stream = torch.cuda.current_stream(device).cuda_stream
-        if head >= 0:  # a one-relation batch reads that head's trie only
-            _native.call("rnnl_node_weights_head", nr.ptr, head, emb_d.data_ptr(), 16, _native.AGG_SUM,
-                         ws_[0].data_ptr(), node_w.data_ptr(), stream)
-        else:
-            _native.call("rnnl_node_weights", nr.ptr, emb_d.data_ptr(), 16, _native.AGG_SUM, ws_[0].data_ptr(),
-                         node_w.data_ptr(), stream)
+        node_w = _train_node_records(nr, _native.AGG_SUM, head, emb_d, ws_[0], stream)
         p = _native.PredictorParams()
         p.aggregator = _native.AGG_SUM
         p.feature = _native.FEATURE_NONE if kind == "none" else _native.FEATURE_ADD
@@ -1052,7 +1010,7 @@ class _PlusSumTrain(torch.autograd.Function):
         mask8 = None
         totals = np.zeros(2, dtype=np.int64)
 
-        def run(ws, scale):
+        def fill():
             if kind == "bias":
                 _native.call("rnnl_fill_rows", bias.data_ptr(), nq, E, score.data_ptr(), stream)
             elif kind == "rows":
@@ -1060,52 +1018,43 @@ class _PlusSumTrain(torch.autograd.Function):
             else:
                 _native.call("rnnl_fill_value", float("-inf"), score.numel(), score.data_ptr(), stream)
                 mask8.zero_()
+
+        def run(ws, scale):
+            fill()
             _native.call("rnnl_predictorplus_forward", g, nr.ptr, ctypes.byref(p), all_h.data_ptr(),
                          all_r.data_ptr(), etr.data_ptr() if etr is not None else None, nq, score.data_ptr(),
                          mask8.data_ptr() if mask8 is not None else None, n_cand.data_ptr(), None, ws.data_ptr(),
                          ws.numel(), scale, stream)
+
+        def score_ahead(ws, scale, n_cand):
+            _native.call("rnnl_predictorplus_score", g, nr.ptr, ctypes.byref(p), all_h.data_ptr(),
+                         all_r.data_ptr(), nq, score.data_ptr(), mask8.data_ptr() if mask8 is not None else None,
+                         n_cand.data_ptr(), None, ws.data_ptr(), ws.numel(), scale, 0, 0, stream)
+
+        def records_in_range():
+            nflag_ev.synchronize()  # (the node records only: the scoring pass runs on)
+            # non-zero: the one-call path, so that RNNL_ERR_RANGE is raised as without the lookahead
+            return int(nflag.view(torch.int32)[0]) == 0
         score = torch.empty((nq, E), dtype=torch.float32, device=device)
         n_cand = torch.empty(nq, dtype=torch.int32, device=device)
         if kind == "none":
             mask8 = torch.empty((nq, E), dtype=torch.uint8, device=device)
         model.check_deferred(keep=1)
-        pre = model._prefetched(device, *raw) if raw is not None else None
-        if pre is not None:
+        pre = model._prefetched(device, raw) if raw is not None else None
+        used = None
+        if pre is not None:  # grounded ahead (prefetch): the scoring half only
             # the node records' range flag (trailer word 2: a non-finite or
             # >= 2^30 aggregate), copied behind rnnl_node_weights*: checked
-            # below before the lookahead's scores are used, so that such a
-            # batch takes the one-call path and its RNNL_ERR_RANGE fallback
-            # (the exact COO path) exactly as without the lookahead
-            nflag, nflag_ev = model._node_flag_slot(device)
-            nflag.copy_(node_w[nbytes.value - 64 + 8:nbytes.value - 64 + 12], non_blocking=True)
+            # before the lookahead's scores are used, so that such a batch
+            # takes the one-call path and its RNNL_ERR_RANGE fallback (the
+            # exact COO path) exactly as without the lookahead
+            nflag, nflag_ev = model._lookahead[model._device_index(device)].node_flag
+            nflag.copy_(node_w[node_w.numel() - 64 + 8:node_w.numel() - 64 + 12], non_blocking=True)
             nflag_ev.record()
-        if pre is not None:  # grounded ahead (prefetch): the scoring half only
-            _, _, _, ws, scale, n_cand_pf, ev, _, hdr = pre
-            ev.synchronize()  # that grounding and its header copy, not the later side-stream work
-            rc = _native.lib().rnnl_forward_status_host(hdr.data_ptr(), totals.ctypes.data_as(ctypes.c_void_p))
-            if rc == _native.RNNL_OK:
-                if kind == "bias":
-                    _native.call("rnnl_fill_rows", bias.data_ptr(), nq, E, score.data_ptr(), stream)
-                elif kind == "rows":
-                    score.copy_(base.detach())
-                else:
-                    _native.call("rnnl_fill_value", float("-inf"), score.numel(), score.data_ptr(), stream)
-                    mask8.zero_()
-                torch.cuda.current_stream(device).wait_event(ev)
-                _native.call("rnnl_predictorplus_score", g, nr.ptr, ctypes.byref(p), all_h.data_ptr(),
-                             all_r.data_ptr(), nq, score.data_ptr(), mask8.data_ptr() if mask8 is not None else None,
-                             n_cand_pf.data_ptr(), None, ws.data_ptr(), ws.numel(), scale, 0, 0, stream)
-                nflag_ev.synchronize()  # (the node records only: the scoring pass runs on)
-                if int(nflag.view(torch.int32)[0]) == 0:
-                    # the scoring pass's remaining range flag (a candidate's
-                    # counts past the exact int64 sums), read two forwards later
-                    model._defer_status(device, ws)
-                    n_cand = n_cand_pf
-                else:  # out of the records' range: the one-call path raises RNNL_ERR_RANGE
-                    pre = None
-            else:  # overflow (or another failure): the one-call path, with its retry
-                pre = None
-        if pre is None:
+            used = model._score_grounded_ahead(device, pre, totals, fill, score_ahead, accept=records_in_range)
+        if used:
+            ws, scale, n_cand = used
+        else:
             ws, scale = model._launch(device, nq, run, totals)
         ctx.no_cand = int(totals[0]) == 0
         ctx.n_total = int(totals[0])
@@ -1186,16 +1135,8 @@ class _PnaStats(torch.autograd.Function):
         nq = all_h.numel()
         nr = model.native_rules(device)
         emb_d = emb.detach().float().contiguous()
-        nbytes = ctypes.c_size_t()
-        _native.call("rnnl_node_weights_size", nr.ptr, _native.AGG_PNA, ctypes.byref(nbytes))
-        node_w = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
         stream = torch.cuda.current_stream(device).cuda_stream
-        if head >= 0:  # a one-relation batch: that head's trie only
-            _native.call("rnnl_node_weights_head", nr.ptr, head, emb_d.data_ptr(), 16, _native.AGG_PNA, None,
-                         node_w.data_ptr(), stream)
-        else:
-            _native.call("rnnl_node_weights", nr.ptr, emb_d.data_ptr(), 16, _native.AGG_PNA, None, node_w.data_ptr(),
-                         stream)
+        node_w = _train_node_records(nr, _native.AGG_PNA, head, emb_d, None, stream)
         totals = np.zeros(2, dtype=np.int64)
         ws, scale, n_cand = model.ground(all_h, all_r, etr, totals)
         C = int(totals[0])
@@ -1414,13 +1355,11 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         # training lookahead (TrainerPredictor.train calls prefetch on the next
         # batches): their grounding runs on a side stream during this step, and
         # the step reads its status and relation without waiting on the GPU
-        self._pf = {}
-        self.prefetch_depth = 2
+        self._lookahead = {}
         # the inference rule encoder over the rule trie (rnnl_lstm_encode_trie,
         # bitwise the per-rule rnnl_lstm_encode with 2.6x fewer LSTM steps on
         # FB15k-237); False: one lane row per rule
         self.encoder_trie = True
-        self.prefetch_dropped = 0
 
     # ------------------------------------------------------------------ rules
     def set_rules(self, input):
@@ -1444,7 +1383,7 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         # scratch sized by the old rules' trie (encoder state, backward, the
         # parameter block) and groundings of the old rules queued ahead
         self._side = {}
-        self._pf = {}
+        self._discard_lookahead()
         self.__dict__.pop("_src_lists", None)
 
     def encode_rules(self, rule_features):
@@ -1842,7 +1781,6 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         device = all_h.device
         all_h = all_h.to(torch.int64)
         all_r = all_r.to(torch.int64)
-        nq, E = all_h.numel(), self.num_entities
         if self.fused and self.aggregator == "sum" and self.fused_backward and device.type == "cuda":
             try:
                 return self._forward_sum_train(all_h, all_r, edges_to_remove, query_r)
@@ -1858,14 +1796,38 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
                     raise
         row, ent, ce, node, count = self.ground_coo(all_h, all_r, edges_to_remove)
         if ent.numel() == 0:
-            # predictors.py:230-237 early return
-            zero = torch.zeros((nq, E), device=device)
-            if self.entity_feature == "bias":
-                return zero + self.bias.unsqueeze(0), torch.ones((nq, E), dtype=torch.bool, device=device)
-            if self.entity_feature == "RotatE":
-                return zero + self.RotatE(all_h, all_r), torch.ones((nq, E), dtype=torch.bool, device=device)
-            return zero - float("-inf"), torch.zeros((nq, E), dtype=torch.bool, device=device)
+            return self._no_candidate(all_h, all_r, autograd=True)
         return self._score_coo(all_h, all_r, row, ent, ce, node, count, rels=query_r)
+
+    def _no_candidate(self, all_h, all_r, autograd):
+        """The reference's early return for a batch without any candidate
+        (predictors.py:230-237): (score, mask) of the entity feature alone.
+        autograd: the reference's expressions (`zero + feature`; without a
+        feature `mask - float('-inf')`, +inf); otherwise the forward_rows
+        contract: the detached base score, or -inf with the mask False."""
+        device = all_h.device
+        nq, E = all_h.numel(), self.num_entities
+        if self.entity_feature not in ("bias", "RotatE"):
+            return (torch.full((nq, E), float("inf" if autograd else "-inf"), device=device),
+                    torch.zeros((nq, E), dtype=torch.bool, device=device))
+        if self.entity_feature == "bias":
+            base = self.bias.unsqueeze(0) if autograd else self.bias.detach().float().unsqueeze(0).expand(
+                nq, E).contiguous()
+        else:
+            base = self.RotatE(all_h, all_r)
+        score = torch.zeros((nq, E), device=device) + base if autograd else base
+        return score, torch.ones((nq, E), dtype=torch.bool, device=device)
+
+    def _train_rule_table(self, device, head, all_r):
+        """The (num_rules, hidden) rule-embedding table of a fused training
+        forward: rule_emb, or the LSTM outputs of the rules of relation `head`
+        (head < 0: of all_r's relations) scattered into a zero table."""
+        if self.type == "emb":
+            return self.rule_emb
+        rels = [head] if head >= 0 else torch.unique(all_r).tolist()
+        ridx = self._rule_ids(rels, device)
+        x_f = self._encode_rules_padded(ridx, device, rels)
+        return torch.zeros((self.num_rules, self.hidden_dim), dtype=x_f.dtype, device=device).index_copy(0, ridx, x_f)
 
     @_native.on_input_device
     def _forward_sum_train(self, all_h, all_r, edges_to_remove, query_r):
@@ -1875,14 +1837,7 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         etr = edges_to_remove.to(device, torch.int64).contiguous() if edges_to_remove is not None else None
         all_h, all_r = all_h.contiguous(), all_r.contiguous()
         head = int(query_r) if isinstance(query_r, int) else -1
-        if self.type == "emb":
-            emb = self.rule_emb
-        else:
-            rels = [head] if head >= 0 else torch.unique(all_r).tolist()
-            ridx = self._rule_ids(rels, device)
-            x_f = self._encode_rules_padded(ridx, device, rels)
-            emb = torch.zeros((self.num_rules, self.hidden_dim), dtype=x_f.dtype, device=device).index_copy(
-                0, ridx, x_f)
+        emb = self._train_rule_table(device, head, all_r)
         if self.entity_feature == "bias":
             kind, base = "bias", self.bias
         elif self.entity_feature == "RotatE":
@@ -1904,27 +1859,14 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         and its dense rest (layers.FuncToNode.finish) and score_model as
         torch layers."""
         device = all_h.device
-        nq, E = all_h.numel(), self.num_entities
         etr = edges_to_remove.to(device, torch.int64).contiguous() if edges_to_remove is not None else None
         all_h, all_r = all_h.contiguous(), all_r.contiguous()
         head = int(query_r) if isinstance(query_r, int) else -1
-        if self.type == "emb":
-            emb = self.rule_emb
-        else:
-            rels = [head] if head >= 0 else torch.unique(all_r).tolist()
-            ridx = self._rule_ids(rels, device)
-            x_f = self._encode_rules_padded(ridx, device, rels)
-            emb = torch.zeros((self.num_rules, self.hidden_dim), dtype=x_f.dtype, device=device).index_copy(
-                0, ridx, x_f)
+        emb = self._train_rule_table(device, head, all_r)
         wsum, wsq, mn, mx, deg, row, ent, row_scale = _PnaStats.apply(self, emb, all_h, all_r, etr, head)
-        if ent.numel() == 0:  # predictors.py:230-237 early return
-            zero = torch.zeros((nq, E), device=device)
-            if self.entity_feature == "bias":
-                return zero + self.bias.unsqueeze(0), torch.ones((nq, E), dtype=torch.bool, device=device)
-            if self.entity_feature == "RotatE":
-                return zero + self.RotatE(all_h, all_r), torch.ones((nq, E), dtype=torch.bool, device=device)
-            return zero - float("-inf"), torch.zeros((nq, E), dtype=torch.bool, device=device)
-        out = self.rule_to_entity.finish(wsum, wsq, mn, mx, deg, row, nq, row_scale=row_scale)
+        if ent.numel() == 0:
+            return self._no_candidate(all_h, all_r, autograd=True)
+        out = self.rule_to_entity.finish(wsum, wsq, mn, mx, deg, row, all_h.numel(), row_scale=row_scale)
         return self._score_tail(all_h, all_r, row, ent, out, head=head)
 
     def _pna_scratch(self, device):
@@ -1945,15 +1887,6 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         _native.call("rnnl_predictorplus_ground", g, nr.ptr, _native.AGG_SUM, h.data_ptr(), r.data_ptr(),
                      etr.data_ptr() if etr is not None else None, nq, n_cand.data_ptr(), ws.data_ptr(), ws.numel(),
                      scale, 0, stream)
-
-    def _node_flag_slot(self, device):
-        """(pinned int32, event): the host copy of a node-record table's range
-        flag for the lookahead training forward (waited on within the call)."""
-        key = ("nflag", self._device_index(device))
-        v = self._side.get(key)
-        if v is None:
-            v = self._side[key] = (torch.zeros(4, dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
-        return v
 
     def _backward_scratch(self, device):
         key = ("bwd", self._device_index(device))
@@ -1976,18 +1909,11 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         device = all_h.device
         all_h = all_h.to(torch.int64)
         all_r = all_r.to(torch.int64)
-        nq, E = all_h.numel(), self.num_entities
         row, ent, ce, node, count = self.ground_coo(all_h, all_r, edges_to_remove)
-        n_cand = torch.zeros(nq, dtype=torch.int32, device=device).index_add_(
+        n_cand = torch.zeros(all_h.numel(), dtype=torch.int32, device=device).index_add_(
             0, row, torch.ones_like(row, dtype=torch.int32))
         if ent.numel() == 0:
-            if self.entity_feature == "bias":
-                return self.bias.detach().float().unsqueeze(0).expand(nq, E).contiguous(), \
-                    torch.ones((nq, E), dtype=torch.bool, device=device), n_cand
-            if self.entity_feature == "RotatE":
-                return self.RotatE(all_h, all_r), torch.ones((nq, E), dtype=torch.bool, device=device), n_cand
-            return torch.full((nq, E), float("-inf"), device=device), \
-                torch.zeros((nq, E), dtype=torch.bool, device=device), n_cand
+            return self._no_candidate(all_h, all_r, autograd=False) + (n_cand,)
         score, mask = self._score_coo(all_h, all_r, row, ent, ce, node, count, nonfinite=nonfinite)
         return score, mask, n_cand
 
@@ -2174,15 +2100,16 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         With autograd active (training) the differentiable path runs
         (forward_autograd); otherwise the fused HIP kernels (forward_rows)."""
         if self._needs_grad():
-            pre = self._prefetched(all_h.device, all_h, all_r, edges_to_remove, peek=True) \
+            pre = self._prefetched(all_h.device, (all_h, all_r, edges_to_remove), peek=True) \
                 if self._prefetch_enabled() and all_h.is_cuda else None
             if pre is not None:
                 # grounded ahead: the one-relation flag and the relation from its
                 # header copy (its event ended long ago: no wait on this step)
-                pre[6].synchronize()
-                _native.call("rnnl_forward_flags_host", pre[8].data_ptr(), self._flags.ctypes.data_as(ctypes.c_void_p))
+                pre.event.synchronize()
+                _native.call("rnnl_forward_flags_host", pre.header.data_ptr(),
+                             self._flags.ctypes.data_as(ctypes.c_void_p))
                 self._check_one_relation()
-                query_r = self._prefetch_relation(pre[8], self._header_bytes())
+                query_r = pre.relation
             else:
                 # the reference's single-relation check (predictors.py:211-212) in one host
                 # read, which also gives the relation whose rules the autograd path gathers
