@@ -119,7 +119,8 @@ struct rnnl_miner_s {
   int32_t ground_blocks = 0;
   unsigned char *eval_scratch = nullptr;  // rnnl_miner_evaluate above its LDS regime; one of bufs
   int32_t eval_blocks = 0;
-  unsigned char *pred_flags = nullptr;  // rnnl_miner_predict above the LDS regime: per workgroup a list (int) and a flag byte per entity
+  // rnnl_miner_predict above its LDS regime: per workgroup a list (int) and a flag byte per entity; one of bufs
+  unsigned char *pred_flags = nullptr;
 };
 
 struct rnnl_graph_s {

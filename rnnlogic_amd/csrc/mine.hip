@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "mine_common.h"  // lower_bound_i
 
 namespace rnnl {
 
@@ -112,19 +113,6 @@ __device__ __forceinline__ int mine_scan(int x, int *s_ws, int &total) {
   total = s_ws[MB / 64];
   __syncthreads();
   return res;
-}
-
-// first index in a[lo, hi) with a[i] >= k
-template <typename P>
-__device__ __forceinline__ int lower_bound_i(P a, int lo, int hi, int k) {
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] < k)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
 }
 
 __global__ __launch_bounds__(MB) void mine_kernel(MinerDev m, int L, unsigned long long *table, int64_t cap,

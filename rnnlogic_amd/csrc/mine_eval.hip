@@ -23,7 +23,8 @@
 // Up to EVAL_LDS_E entities val and the integer scratch live in LDS (104 bytes
 // per entity, sized by the graph), above that in a per-workgroup global
 // scratch kept in the handle.  The grounding of a round and the round into val
-// are in mine_ground.h, which the predictions (mine_predict.hip) run as well.
+// are in mine_ground.h, which the predictions (mine_predict.hip) run as well; a
+// hop of the grounding is ground_hop of mine_common.h, the one ground_kernel runs.
 //
 // The head side (rnnl_miner_evaluate_side with RNNL_MINER_HEAD):
 // val[e] = sum of wt[k] * (double)#paths(e -> t along the body), grounded
@@ -35,16 +36,14 @@
 #include <algorithm>
 
 #include "internal.h"
-#include "mine_ground.h"  // the layout, the grounding of a round and the round into val: shared with mine_predict.hip
+#include "mine_ground.h"  // the layout, a round's grounding, the round into val, the known answers, the launch
 
 namespace rnnl {
 
 struct EvalArgs {
   const int32_t *queries;
   int64_t n;
-  const int64_t *known_keys, *known_offs;
-  const int32_t *known_vals;
-  int64_t n_keys;
+  KnownLists known;
   int32_t *ranks;
   double *val_out;
   unsigned char *scratch;
@@ -53,13 +52,11 @@ struct EvalArgs {
 
 template <bool SMALL, bool HEAD>
 __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, EvalArgs a) {
-  extern __shared__ unsigned long long eval_smem[];
   __shared__ int s_n[EW], s_na[EW], s_g[EW], s_ge[EW];
   const int E = d.E, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  unsigned char *base = SMALL ? reinterpret_cast<unsigned char *>(eval_smem)
-                              : a.scratch + (size_t)blockIdx.x * EVAL_PER_E * (size_t)E;
-  double *val = reinterpret_cast<double *>(base);
-  unsigned char *ints = base + 8 * (size_t)E;  // wave w: counts A, counts B (u64 x E), list A, list B (int x E)
+  const QueryArrays q = query_arrays<SMALL>(a.scratch, E);
+  double *val = q.val;
+  unsigned char *ints = q.ints;
   if (SMALL) eval_zero_ints(ints, E);
   __syncthreads();
 #pragma unroll 1
@@ -67,7 +64,7 @@ __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, E
     const int h = a.queries[3 * qi], r = a.queries[3 * qi + 1], t = a.queries[3 * qi + 2];
     if ((unsigned)h >= (unsigned)E || (unsigned)t >= (unsigned)E || (unsigned)r >= (unsigned)d.R) {
       if (tid == 0) {
-        atomicOr(&a.flags[E_INVALID], 1ull);
+        atomicOr(&a.flags[CTR_INVALID], 1ull);
         a.ranks[2 * qi] = 0;
         a.ranks[2 * qi + 1] = 0;
       }
@@ -83,7 +80,7 @@ __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, E
       eval_ground_round<HEAD>(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
       eval_round_into_val<false>(l, ints, E, rb, jb, nw, s_na, val, nullptr, nullptr, nullptr, wide);
     }
-    if (wide) atomicOr(&a.flags[E_RANGE], 1ull);
+    if (wide) atomicOr(&a.flags[CTR_RANGE], 1ull);
     __syncthreads();
     const double t_val = val[ans];
     int g = 0, ge = 0;
@@ -95,27 +92,15 @@ __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, E
         ge += v >= t_val;
       }
     }
-    if (a.known_keys) {  // minus the other known tails of (h, r) / known heads of (r, t)
-      const int64_t key = (int64_t)r * E + anc;
-      int64_t lo = 0, hi = a.n_keys;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a.known_keys[mid] < key)
-          lo = mid + 1;
-        else
-          hi = mid;
+    int64_t b0, b1;  // minus the other known tails of (h, r) / known heads of (r, t)
+    if (known_range(a.known, r, anc, E, b0, b1))
+      for (int64_t i = b0 + tid; i < b1; i += EB) {
+        const int e = a.known.vals[i];
+        if (known_skip(a.known.vals, i, b0, e, E, ans)) continue;
+        const double v = val[e];
+        g -= v > t_val;
+        ge -= v >= t_val;
       }
-      if (lo < a.n_keys && a.known_keys[lo] == key) {
-        const int64_t b0 = a.known_offs[lo], b1 = a.known_offs[lo + 1];
-        for (int64_t i = b0 + tid; i < b1; i += EB) {
-          const int e = a.known_vals[i];
-          if ((unsigned)e >= (unsigned)E || e == ans || (i > b0 && a.known_vals[i - 1] == e)) continue;
-          const double v = val[e];
-          g -= v > t_val;
-          ge -= v >= t_val;
-        }
-      }
-    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       g += __shfl_down(g, o, 64);
@@ -162,47 +147,19 @@ int rnnl_miner_set_weights(rnnl_miner m, const double *weights, void *stream) {
 int rnnl_miner_evaluate_side(rnnl_miner m, int32_t side, const int32_t *queries, int64_t n,
                              const int64_t *known_keys, const int64_t *known_offs, const int32_t *known_vals,
                              int64_t n_keys, int32_t *ranks, double *val, uint64_t *counters, void *stream) {
-  if (side != RNNL_MINER_TAIL && side != RNNL_MINER_HEAD) {
-    set_error("rnnl_miner_evaluate_side: side must be RNNL_MINER_TAIL or RNNL_MINER_HEAD");
-    return RNNL_ERR_INVALID;
-  }
-  const bool head = side == RNNL_MINER_HEAD;
-  const bool none = !known_keys && !known_offs && !known_vals;
-  const bool all = known_keys && known_offs && known_vals && n_keys >= 0;
-  if (!m || !m->l.rule_off || n < 0 || (n > 0 && (!queries || !ranks)) || !counters || !(none || all)) {
+  if (!check_side("rnnl_miner_evaluate", side)) return RNNL_ERR_INVALID;
+  EvalArgs a = {};
+  const bool known_ok = known_lists(known_keys, known_offs, known_vals, n_keys, a.known);
+  if (!m || !m->l.rule_off || n < 0 || (n > 0 && (!queries || !ranks)) || !counters || !known_ok) {
     set_error("rnnl_miner_evaluate: bad arguments (set the rules first; the known-answer arrays all or none)");
     return RNNL_ERR_INVALID;
   }
-  hipStream_t st = (hipStream_t)stream;
-  RNNL_HIP_CHECK(hipMemsetAsync(counters, 0, 4 * 8, st));
-  if (n == 0) return RNNL_OK;
-  EvalArgs a = {};
   a.queries = queries;
   a.n = n;
-  if (all && n_keys > 0) {
-    a.known_keys = known_keys;
-    a.known_offs = known_offs;
-    a.known_vals = known_vals;
-    a.n_keys = n_keys;
-  }
   a.ranks = ranks;
   a.val_out = val;
-  a.flags = reinterpret_cast<unsigned long long *>(counters);
-  const size_t E = (size_t)m->d.E;
-  if (m->d.E <= EVAL_LDS_E) {
-    const unsigned grid = (unsigned)std::min<int64_t>(n, EVAL_MAX_BLOCKS);
-    auto kernel = head ? eval_kernel<true, true> : eval_kernel<true, false>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), EVAL_PER_E * E, st, m->d, m->l, a);
-  } else {
-    const int rc = eval_scratch_ensure(m, "rnnl_miner_evaluate");
-    if (rc != RNNL_OK) return rc;
-    a.scratch = m->eval_scratch;
-    const unsigned grid = (unsigned)std::min<int64_t>(n, m->eval_blocks);
-    auto kernel = head ? eval_kernel<false, true> : eval_kernel<false, false>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
-  }
-  RNNL_HIP_CHECK(hipGetLastError());
-  return RNNL_OK;
+  return query_launch(m, "rnnl_miner_evaluate", side, n, 0, a, counters, stream,
+                      [](auto small, auto head) { return eval_kernel<decltype(small)::value, decltype(head)::value>; });
 }
 
 int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const int64_t *known_keys,

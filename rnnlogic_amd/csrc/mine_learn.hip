@@ -30,21 +30,17 @@
 #include <vector>
 
 #include "internal.h"
+#include "mine_common.h"  // the counters, the scratch of a grounding and its hop: the one the query kernels run
 
 namespace rnnl {
 
-constexpr int GB = 64;          // ground: threads per workgroup (one wave)
+constexpr int GB = 64;          // ground: threads per workgroup (one wave, as ground_hop takes it)
 constexpr int LB = 1024;        // learn / hscore: threads per workgroup (lanes over a relation's rules)
 constexpr int SMALL_E = 2048;   // dense per-relation arrays live in LDS up to this many entities
 constexpr size_t GROUND_SCRATCH = 256u << 20;
 
-enum : int { F_TOTAL = 0, F_RANGE = 1, F_INVALID = 2, F_INTERNAL = 3 };
-
-__device__ __forceinline__ unsigned long long ld_u64(unsigned long long *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// first index in [lo, hi) of the (relation, target)-sorted edges with (rel, dst) >= (r, x)
+// first index in [lo, hi) of the (relation, target)-sorted edges with (rel, dst) >= (r, x): the target lookup of
+// learn_triple (the run of a relation alone is lower_bound_i on rel)
 __device__ __forceinline__ int edge_lower(const int32_t *rel, const int32_t *dst, int lo, int hi, int r, int x) {
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
@@ -70,7 +66,10 @@ __device__ __forceinline__ int pair_triple(const int64_t *pair_base, int count, 
   return lo;
 }
 
-// Per-workgroup scratch: counts A, counts B (u64 x E each), list A, list B (int x E each).
+// Per-workgroup scratch: one GroundScratch block.  A hop is the tail side of
+// ground_hop; its report of a count past 32 bits carried over an inner hop is
+// not used here: only the final counts become entries, so only they raise
+// CTR_RANGE (the query kernels raise it on any hop: mine_ground.h).
 template <bool FILL>
 __global__ __launch_bounds__(GB) void ground_kernel(MinerDev d, MinerLearnDev l, const int32_t *__restrict__ order,
                                                     int64_t begin, int32_t count,
@@ -79,9 +78,7 @@ __global__ __launch_bounds__(GB) void ground_kernel(MinerDev d, MinerLearnDev l,
                                                     uint32_t *__restrict__ ent_cnt, int64_t ent_cap,
                                                     unsigned char *scratch, unsigned long long *flags) {
   const int E = d.E, tid = threadIdx.x;
-  unsigned long long *c0 = reinterpret_cast<unsigned long long *>(scratch + (size_t)blockIdx.x * 24 * (size_t)E);
-  unsigned long long *c1 = c0 + E;
-  int *l0 = reinterpret_cast<int *>(c1 + E), *l1 = l0 + E;
+  const GroundScratch s0(scratch, blockIdx.x, E);
   __shared__ int s_n;
 #pragma unroll 1
   for (int64_t pair = blockIdx.x; pair < npairs; pair += gridDim.x) {
@@ -96,56 +93,43 @@ __global__ __launch_bounds__(GB) void ground_kernel(MinerDev d, MinerLearnDev l,
       if (rule < l.rule_off[r + 1])
         len = l.rule_len[rule];
       else if (tid == 0)
-        atomicOr(&flags[F_INTERNAL], 1ull);
+        atomicOr(&flags[CTR_INTERNAL], 1ull);
     } else if (tid == 0) {
-      atomicOr(&flags[F_INVALID], 1ull);
+      atomicOr(&flags[CTR_INVALID], 1ull);
     }
-    unsigned long long *ca = c0, *cb = c1;
-    int *la = l0, *lb = l1;
+    GroundScratch s = s0;
     int na = 0;
     if (len > 0) {
       if (tid == 0) {
-        la[0] = h;
-        ca[h] = 1;
+        s.la[0] = h;
+        s.ca[h] = 1;
       }
       na = 1;
     }
     __syncthreads();
     for (int k = 0; k < len; ++k) {
-      const int rel = l.rule_body[RULE_STRIDE * rule + k];
       if (tid == 0) s_n = 0;
       __syncthreads();
-      for (int i = tid; i < na; i += GB) {
-        const int e = la[i];
-        const unsigned long long n = ld_u64(&ca[e]);
-        const int en = d.out_off[e + 1];
-        for (int a = edge_lower(l.so_rel, l.so_dst, d.out_off[e], en, rel, 0); a < en && l.so_rel[a] == rel; ++a) {
-          const int x = l.so_dst[a];
-          if (e == h && rel == r && x == t) continue;  // the triple's own edge, and every copy of it
-          if (atomicAdd(&cb[x], n) == 0) lb[atomicAdd(&s_n, 1)] = x;
-        }
-      }
+      bool inner = false;  // a count past 32 bits on the way: not reported, see above
+      ground_hop<false>(d, l, s, na, tid, l.rule_body[RULE_STRIDE * rule + k], h, r, t, &s_n, inner);
       __syncthreads();
-      for (int i = tid; i < na; i += GB) ca[la[i]] = 0;
+      for (int i = tid; i < na; i += GB) s.ca[s.la[i]] = 0;
       na = s_n;
       __syncthreads();
-      unsigned long long *tc = ca;
-      ca = cb;
-      cb = tc;
-      int *tl = la;
-      la = lb;
-      lb = tl;
+      s.swap();
     }
     // la[0, na) are the destinations, ca[] their path counts
+    unsigned long long *ca = s.ca;
+    const int *la = s.la;
     bool wide = false;
     for (int i = tid; i < na; i += GB) wide |= ld_u64(&ca[la[i]]) > 0xffffffffull;
-    if (wide) atomicOr(&flags[F_RANGE], 1ull);
+    if (wide) atomicOr(&flags[CTR_RANGE], 1ull);
     if (!FILL) {
       if (tid == 0) pair_off[pair] = na;
     } else {
       const int64_t base = pair_off[pair];
       if (pair_off[pair + 1] - base != na || base < 0 || base + na > ent_cap) {
-        if (tid == 0) atomicOr(&flags[F_INTERNAL], 1ull);
+        if (tid == 0) atomicOr(&flags[CTR_INTERNAL], 1ull);
       } else if (na <= GB) {
         if (tid < na) {
           const int x = la[tid];
@@ -175,7 +159,7 @@ __global__ __launch_bounds__(GB) void ground_kernel(MinerDev d, MinerLearnDev l,
   }
 }
 
-// In-place exclusive scan of a[0, n) by one workgroup; a[n] and flags[F_TOTAL] get the total.
+// In-place exclusive scan of a[0, n) by one workgroup; a[n] and flags[CTR_TOTAL] get the total.
 __global__ __launch_bounds__(1024) void scan_kernel(int64_t *a, int64_t n, unsigned long long *flags) {
   __shared__ long long ws[17];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -207,7 +191,7 @@ __global__ __launch_bounds__(1024) void scan_kernel(int64_t *a, int64_t n, unsig
   }
   if (tid == 0) {
     a[n] = (int64_t)carry;
-    flags[F_TOTAL] = (unsigned long long)carry;
+    flags[CTR_TOTAL] = (unsigned long long)carry;
   }
 }
 
@@ -548,15 +532,16 @@ static int set_rules_impl(rnnl_miner m, const int32_t *rule_off, const int32_t *
   m->l.si_rel = keep.si_rel;
   m->l.si_src = keep.si_src;
   m->l.n_rules = n;
-  // workgroups of the grounding pass: bounded by their scratch (24 bytes per entity each)
-  m->ground_blocks = (int32_t)std::max<size_t>(64, std::min<size_t>(4096, GROUND_SCRATCH / (24 * (size_t)E)));
+  // workgroups of the grounding pass: bounded by their scratch (GROUND_PER_E bytes per entity each)
+  m->ground_blocks =
+      (int32_t)std::max<size_t>(64, std::min<size_t>(4096, GROUND_SCRATCH / (GROUND_PER_E * (size_t)E)));
   void *p_off, *p_len, *p_body, *p_prior, *p_state, *p_gs, *p_cs;
   int rc = dev_alloc(m, (size_t)(R + 1) * 4, &p_off);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 4, &p_len);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 4 * RULE_STRIDE, &p_body);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 8, &p_prior);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 8 * 6, &p_state);
-  if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)m->ground_blocks * 24 * (size_t)E, &p_gs);
+  if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)m->ground_blocks * GROUND_PER_E * (size_t)E, &p_gs);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)R * 16 * (size_t)E, &p_cs);
   if (rc != RNNL_OK) {
     set_error(who + ": device allocation failed");
@@ -572,7 +557,7 @@ static int set_rules_impl(rnnl_miner m, const int32_t *rule_off, const int32_t *
       RNNL_HIP_CHECK(hipMemset(p_prior, 0, (size_t)n * 8));
   }
   RNNL_HIP_CHECK(hipMemset(p_state, 0, std::max<size_t>((size_t)n * 8 * 6, 8)));
-  RNNL_HIP_CHECK(hipMemset(p_gs, 0, (size_t)m->ground_blocks * 24 * (size_t)E));
+  RNNL_HIP_CHECK(hipMemset(p_gs, 0, (size_t)m->ground_blocks * GROUND_PER_E * (size_t)E));
   m->l.rule_off = static_cast<const int32_t *>(p_off);
   m->l.rule_len = static_cast<const int32_t *>(p_len);
   m->l.rule_body = static_cast<const int32_t *>(p_body);

@@ -69,9 +69,7 @@ static_assert(PRED_K_MAX == EB, "one sort slot per thread");
 struct PredArgs {
   const int32_t *queries;
   int64_t n;
-  const int64_t *known_keys, *known_offs;
-  const int32_t *known_vals;
-  int64_t n_keys;
+  KnownLists known;
   int32_t k, all, blocks;  // blocks: the workgroups flag_scratch is cut for
   int32_t *index;
   double *score;
@@ -118,7 +116,6 @@ enum : int { C_TOUCHED, C_ELIG, C_AHEAD, C_SURV, C_KNOWN, C_KNOWN_LT, C_TOUCHED_
 
 template <bool SMALL, bool HEAD>
 __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l, PredArgs a) {
-  extern __shared__ unsigned long long eval_smem[];
   __shared__ int s_n[EW], s_na[EW];
   __shared__ unsigned int s_hist[256], s_wtot[EW], s_sel[3];
   __shared__ unsigned long long s_key[PRED_K_MAX];
@@ -127,15 +124,16 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
   // and those of them below the answer; touched entities below the answer; candidates (touched + appended)
   __shared__ int s_cnt[C_N];
   const int E = d.E, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  unsigned char *base = SMALL ? reinterpret_cast<unsigned char *>(eval_smem)
-                              : a.scratch + (size_t)blockIdx.x * EVAL_PER_E * (size_t)E;
-  double *val = reinterpret_cast<double *>(base);
-  unsigned char *ints = base + 8 * (size_t)E;
-  // the candidate list (int x E) and the flag bytes (E): after eval_kernel's arrays / in scratch of their own
-  int *cand = SMALL ? reinterpret_cast<int *>(base + EVAL_PER_E * (size_t)E)
+  const QueryArrays q = query_arrays<SMALL>(a.scratch, E);
+  double *val = q.val;
+  unsigned char *ints = q.ints;
+  // the candidate list (int x E) and the flag bytes (E): after eval_kernel's arrays / in scratch of their own, the
+  // lists of all workgroups first
+  int *cand = SMALL ? reinterpret_cast<int *>(q.base + EVAL_PER_E * (size_t)E)
                     : reinterpret_cast<int *>(a.flag_scratch) + (size_t)blockIdx.x * (size_t)E;
-  unsigned char *flg = SMALL ? base + (EVAL_PER_E + 4) * (size_t)E
-                             : a.flag_scratch + 4 * (size_t)a.blocks * (size_t)E + (size_t)blockIdx.x * (size_t)E;
+  unsigned char *flg = SMALL ? q.base + (EVAL_PER_E + PRED_LIST_PER_E) * (size_t)E
+                             : a.flag_scratch + PRED_LIST_PER_E * (size_t)a.blocks * (size_t)E +
+                                   (size_t)blockIdx.x * (size_t)E;
   int nb = 1;  // bytes of the entity part of a composite
   while (nb < 4 && ((unsigned)(E - 1) >> (8 * nb)) != 0) ++nb;
   if (SMALL) eval_zero_ints(ints, E);
@@ -154,7 +152,7 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
         a.score[qi * a.k + tid] = -INFINITY;
       }
       if (tid == 0) {
-        atomicOr(&a.flags[E_INVALID], 1ull);
+        atomicOr(&a.flags[CTR_INVALID], 1ull);
         a.valid[qi] = 0;
         a.position[qi] = -1;
       }
@@ -172,30 +170,16 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
       eval_ground_round<HEAD>(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
       eval_round_into_val<true>(l, ints, E, rb, jb, nw, s_na, val, flg, cand, &s_cnt[C_TOUCHED], wide);
     }
-    if (wide) atomicOr(&a.flags[E_RANGE], 1ull);
+    if (wide) atomicOr(&a.flags[CTR_RANGE], 1ull);
     __syncthreads();
     const int nt = s_cnt[C_TOUCHED];
     // the other known tails of (h, r) / heads of (r, t) leave (bit 1); those no rule reached are counted for `all`
-    int64_t kb0 = 0, kb1 = 0;
-    if (a.known_keys) {
-      const int64_t key = (int64_t)r * E + anc;
-      int64_t lo = 0, hi = a.n_keys;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a.known_keys[mid] < key)
-          lo = mid + 1;
-        else
-          hi = mid;
-      }
-      if (lo < a.n_keys && a.known_keys[lo] == key) {
-        kb0 = a.known_offs[lo];
-        kb1 = a.known_offs[lo + 1];
-      }
-    }
+    int64_t kb0, kb1;
+    known_range(a.known, r, anc, E, kb0, kb1);
     int kn = 0, knlt = 0;
     for (int64_t i = kb0 + tid; i < kb1; i += EB) {
-      const int e = a.known_vals[i];
-      if ((unsigned)e >= (unsigned)E || e == ans || (i > kb0 && a.known_vals[i - 1] == e)) continue;
+      const int e = a.known.vals[i];
+      if (known_skip(a.known.vals, i, kb0, e, E, ans)) continue;
       const int f = flg[e];  // one thread per distinct e: the lists are ascending within a key
       flg[e] = f | 2;
       if (!(f & 1)) {
@@ -361,7 +345,7 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
       }
     }
     __syncthreads();
-    if (overflow || (tid == 0 && s_cnt[C_SURV] != nsel)) atomicOr(&a.flags[E_INTERNAL], 1ull);
+    if (overflow || (tid == 0 && s_cnt[C_SURV] != nsel)) atomicOr(&a.flags[CTR_INTERNAL], 1ull);
     if (nsel > 1) {  // bitonic network over the PRED_K_MAX slots, one per thread
 #pragma unroll 1
       for (int size = 2; size <= PRED_K_MAX; size <<= 1) {
@@ -401,7 +385,7 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
       flg[x] = 0;
     }
     for (int64_t i = kb0 + tid; i < kb1; i += EB) {
-      const int e = a.known_vals[i];
+      const int e = a.known.vals[i];
       if ((unsigned)e < (unsigned)E) flg[e] = 0;
     }
     __syncthreads();
@@ -410,12 +394,9 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
 
 template <bool SMALL, bool HEAD>
 __global__ __launch_bounds__(EB) void explain_kernel(MinerDev d, MinerLearnDev l, ExplArgs a) {
-  extern __shared__ unsigned long long eval_smem[];
   __shared__ int s_n[EW], s_na[EW];
   const int E = d.E, tid = threadIdx.x;
-  unsigned char *base = SMALL ? reinterpret_cast<unsigned char *>(eval_smem)
-                              : a.scratch + (size_t)blockIdx.x * EVAL_PER_E * (size_t)E;
-  unsigned char *ints = base + 8 * (size_t)E;  // the layout of eval_kernel; val is not used
+  unsigned char *ints = query_arrays<SMALL>(a.scratch, E).ints;  // the layout of eval_kernel; val is not used
   if (SMALL) eval_zero_ints(ints, E);
   __syncthreads();
 #pragma unroll 1
@@ -429,7 +410,7 @@ __global__ __launch_bounds__(EB) void explain_kernel(MinerDev d, MinerLearnDev l
     if (tid < a.m) {
       ent = bad ? -1 : a.index[slot];
       if (ent < -1 || ent >= E) {
-        atomicOr(&a.flags[E_INVALID], 1ull);
+        atomicOr(&a.flags[CTR_INVALID], 1ull);
         ent = -1;
       }
       for (int j = 0; j < a.c; ++j) {
@@ -440,7 +421,7 @@ __global__ __launch_bounds__(EB) void explain_kernel(MinerDev d, MinerLearnDev l
       a.total[slot] = 0.0;
     }
     if (bad) {
-      if (tid == 0) atomicOr(&a.flags[E_INVALID], 1ull);
+      if (tid == 0) atomicOr(&a.flags[CTR_INVALID], 1ull);
       continue;
     }
     const int rb = l.rule_off[r], nr = l.rule_off[r + 1] - rb;
@@ -454,11 +435,9 @@ __global__ __launch_bounds__(EB) void explain_kernel(MinerDev d, MinerLearnDev l
       for (int w = 0; w < nw; ++w) {  // the round's rules one after the other: list order per slot
         const int len2 = l.rule_len[rb + jb + w];
         if (len2 == 0) continue;  // an empty body reaches nothing
-        unsigned long long *fc;
-        const int *fl;
-        eval_final(ints, E, w, len2, fc, fl);
+        const GroundScratch f = eval_final(ints, E, w, len2);
         if (ent >= 0) {
-          const unsigned long long c = eval_ld_u64(&fc[ent]);  // 0 wherever the rule does not arrive
+          const unsigned long long c = ld_u64(&f.ca[ent]);  // 0 wherever the rule does not arrive
           if (c > 0) {
             const double term = l.wt[rb + jb + w] * (double)c;
             tot = tot + term;
@@ -479,14 +458,14 @@ __global__ __launch_bounds__(EB) void explain_kernel(MinerDev d, MinerLearnDev l
         __syncthreads();
         const int n2 = s_na[w];
         for (int i = tid; i < n2; i += EB) {
-          const int x = fl[i];
-          wide |= eval_ld_u64(&fc[x]) > 0xffffffffull;
-          fc[x] = 0;
+          const int x = f.la[i];
+          wide |= ld_u64(&f.ca[x]) > 0xffffffffull;
+          f.ca[x] = 0;
         }
         __syncthreads();
       }
     }
-    if (wide) atomicOr(&a.flags[E_RANGE], 1ull);
+    if (wide) atomicOr(&a.flags[CTR_RANGE], 1ull);
     if (tid < a.m) {
       a.fired[slot] = nf;
       a.total[slot] = tot;
@@ -505,11 +484,7 @@ int rnnl_miner_predict_side(rnnl_miner m, int32_t side, const int32_t *queries, 
                             const int64_t *known_offs, const int32_t *known_vals, int64_t n_keys, int32_t k,
                             int32_t candidates, int32_t *index, double *score, int32_t *valid, int32_t *position,
                             uint64_t *counters, void *stream) {
-  if (side != RNNL_MINER_TAIL && side != RNNL_MINER_HEAD) {
-    set_error("rnnl_miner_predict_side: side must be RNNL_MINER_TAIL or RNNL_MINER_HEAD");
-    return RNNL_ERR_INVALID;
-  }
-  const bool head = side == RNNL_MINER_HEAD;
+  if (!check_side("rnnl_miner_predict", side)) return RNNL_ERR_INVALID;
   if (k < 1 || k > RNNL_MINER_TOPK_MAX) {
     set_error("rnnl_miner_predict: k must be 1.." + std::to_string(RNNL_MINER_TOPK_MAX));
     return RNNL_ERR_INVALID;
@@ -518,9 +493,8 @@ int rnnl_miner_predict_side(rnnl_miner m, int32_t side, const int32_t *queries, 
     set_error("rnnl_miner_predict: candidates must be RNNL_MINER_REACHED or RNNL_MINER_ALL");
     return RNNL_ERR_INVALID;
   }
-  const bool none = !known_keys && !known_offs && !known_vals;
-  const bool all = known_keys && known_offs && known_vals && n_keys >= 0;
-  if (!(none || all)) {
+  PredArgs a = {};
+  if (!known_lists(known_keys, known_offs, known_vals, n_keys, a.known)) {
     set_error("rnnl_miner_predict: the known-answer arrays all or none");
     return RNNL_ERR_INVALID;
   }
@@ -532,51 +506,31 @@ int rnnl_miner_predict_side(rnnl_miner m, int32_t side, const int32_t *queries, 
     set_error("rnnl_miner_predict: bad arguments (n >= 0, no null array)");
     return RNNL_ERR_INVALID;
   }
-  hipStream_t st = (hipStream_t)stream;
-  RNNL_HIP_CHECK(hipMemsetAsync(counters, 0, 4 * 8, st));
-  if (n == 0) return RNNL_OK;
-  PredArgs a = {};
   a.queries = queries;
   a.n = n;
-  if (all && n_keys > 0) {
-    a.known_keys = known_keys;
-    a.known_offs = known_offs;
-    a.known_vals = known_vals;
-    a.n_keys = n_keys;
-  }
   a.k = k;
   a.all = candidates == RNNL_MINER_ALL;
   a.index = index;
   a.score = score;
   a.valid = valid;
   a.position = position;
-  a.flags = reinterpret_cast<unsigned long long *>(counters);
-  const size_t E = (size_t)m->d.E;
-  if (m->d.E <= EVAL_LDS_E) {
-    const unsigned grid = (unsigned)std::min<int64_t>(n, EVAL_MAX_BLOCKS);
-    auto kernel = head ? predict_kernel<true, true> : predict_kernel<true, false>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), (EVAL_PER_E + 5) * E, st, m->d, m->l, a);
-  } else {
-    const int rc = eval_scratch_ensure(m, "rnnl_miner_predict");
-    if (rc != RNNL_OK) return rc;
-    if (!m->pred_flags) {
-      void *p = nullptr;
-      if (hipMalloc(&p, (size_t)m->eval_blocks * 5 * E) != hipSuccess) {  // per workgroup: the list (int), the flags
-        set_error("rnnl_miner_predict: device allocation failed");
-        return RNNL_ERR_NOMEM;
-      }
-      m->bufs.push_back(p);
-      m->pred_flags = static_cast<unsigned char *>(p);
-    }
-    a.scratch = m->eval_scratch;
-    a.flag_scratch = m->pred_flags;
-    a.blocks = m->eval_blocks;
-    const unsigned grid = (unsigned)std::min<int64_t>(n, m->eval_blocks);
-    auto kernel = head ? predict_kernel<false, true> : predict_kernel<false, false>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
-  }
-  RNNL_HIP_CHECK(hipGetLastError());
-  return RNNL_OK;
+  return query_launch(
+      m, "rnnl_miner_predict", side, n, PRED_PER_E, a, counters, stream,
+      [](auto small, auto head) { return predict_kernel<decltype(small)::value, decltype(head)::value>; },
+      [&]() {  // the lists and flags of the scratch's workgroups, in a buffer of their own
+        if (!m->pred_flags) {
+          void *p = nullptr;
+          if (hipMalloc(&p, (size_t)m->eval_blocks * PRED_PER_E * (size_t)m->d.E) != hipSuccess) {
+            set_error("rnnl_miner_predict: device allocation failed");
+            return (int)RNNL_ERR_NOMEM;
+          }
+          m->bufs.push_back(p);
+          m->pred_flags = static_cast<unsigned char *>(p);
+        }
+        a.flag_scratch = m->pred_flags;
+        a.blocks = m->eval_blocks;
+        return (int)RNNL_OK;
+      });
 }
 
 int rnnl_miner_predict(rnnl_miner m, const int32_t *queries, int64_t n, const int64_t *known_keys,
@@ -590,11 +544,7 @@ int rnnl_miner_predict(rnnl_miner m, const int32_t *queries, int64_t n, const in
 int rnnl_miner_explain_side(rnnl_miner m, int32_t side, const int32_t *queries, int64_t n, const int32_t *index,
                             int32_t n_slots, int32_t c, int32_t *fired, double *total, int32_t *rule, int64_t *count,
                             uint64_t *counters, void *stream) {
-  if (side != RNNL_MINER_TAIL && side != RNNL_MINER_HEAD) {
-    set_error("rnnl_miner_explain_side: side must be RNNL_MINER_TAIL or RNNL_MINER_HEAD");
-    return RNNL_ERR_INVALID;
-  }
-  const bool head = side == RNNL_MINER_HEAD;
+  if (!check_side("rnnl_miner_explain", side)) return RNNL_ERR_INVALID;
   if (n_slots < 1 || n_slots > RNNL_MINER_TOPK_MAX) {
     set_error("rnnl_miner_explain: m (the slots per query) must be 1.." + std::to_string(RNNL_MINER_TOPK_MAX));
     return RNNL_ERR_INVALID;
@@ -611,9 +561,6 @@ int rnnl_miner_explain_side(rnnl_miner m, int32_t side, const int32_t *queries, 
     set_error("rnnl_miner_explain: bad arguments (n >= 0, no null array)");
     return RNNL_ERR_INVALID;
   }
-  hipStream_t st = (hipStream_t)stream;
-  RNNL_HIP_CHECK(hipMemsetAsync(counters, 0, 4 * 8, st));
-  if (n == 0) return RNNL_OK;
   ExplArgs a = {};
   a.queries = queries;
   a.n = n;
@@ -624,22 +571,9 @@ int rnnl_miner_explain_side(rnnl_miner m, int32_t side, const int32_t *queries, 
   a.total = total;
   a.rule = rule;
   a.count = reinterpret_cast<long long *>(count);
-  a.flags = reinterpret_cast<unsigned long long *>(counters);
-  const size_t E = (size_t)m->d.E;
-  if (m->d.E <= EVAL_LDS_E) {
-    const unsigned grid = (unsigned)std::min<int64_t>(n, EVAL_MAX_BLOCKS);
-    auto kernel = head ? explain_kernel<true, true> : explain_kernel<true, false>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), EVAL_PER_E * E, st, m->d, m->l, a);
-  } else {
-    const int rc = eval_scratch_ensure(m, "rnnl_miner_explain");
-    if (rc != RNNL_OK) return rc;
-    a.scratch = m->eval_scratch;
-    const unsigned grid = (unsigned)std::min<int64_t>(n, m->eval_blocks);
-    auto kernel = head ? explain_kernel<false, true> : explain_kernel<false, false>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
-  }
-  RNNL_HIP_CHECK(hipGetLastError());
-  return RNNL_OK;
+  return query_launch(m, "rnnl_miner_explain", side, n, 0, a, counters, stream, [](auto small, auto head) {
+    return explain_kernel<decltype(small)::value, decltype(head)::value>;
+  });
 }
 
 int rnnl_miner_explain(rnnl_miner m, const int32_t *queries, int64_t n, const int32_t *index, int32_t n_slots,

@@ -35,6 +35,7 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "mine_common.h"  // the counter slots and lower_bound_i
 
 namespace rnnl {
 
@@ -48,8 +49,6 @@ constexpr size_t STATS_SCRATCH = 256u << 20;
 constexpr int STATS_MAX_BLOCKS = 2048;
 constexpr unsigned STAMP_ROOM = RULE_STRIDE + 1;  // stamps one unit takes at the most
 
-enum : int { S_INVALID = 2, S_INTERNAL = 3 };
-
 struct StatsArgs {
   const int32_t *body_len, *body_rel, *head_off, *head_rel;  // n_bodies, n_bodies x RULE_STRIDE, n_bodies + 1, slots
   int64_t n_items;
@@ -61,18 +60,6 @@ struct StatsArgs {
 };
 
 namespace {
-
-// first index in [lo, hi) of the (relation, target)-sorted edges with relation >= r
-__device__ __forceinline__ int stats_edge_lower(const int32_t *rel, int lo, int hi, int r) {
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (rel[mid] < r)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
 
 // what one wave wrote becomes visible to its other lanes: the stores complete, nothing moves across
 __device__ __forceinline__ void wave_sync() {
@@ -130,7 +117,7 @@ __global__ __launch_bounds__(SB) void stats_kernel(MinerDev d, MinerLearnDev l, 
         const int eb = d.out_off[x], en = d.out_off[x + 1];
         bool go = len == 0;
         if (!go) {
-          const int k = stats_edge_lower(l.so_rel, eb, en, rels[0]);
+          const int k = lower_bound_i(l.so_rel, eb, en, rels[0]);
           go = k < en && l.so_rel[k] == rels[0];
         }
         if (go) s_src[atomicAdd(&s_nsrc, 1)] = x;
@@ -165,7 +152,7 @@ __global__ __launch_bounds__(SB) void stats_kernel(MinerDev d, MinerLearnDev l, 
           for (int i = 0; i < na; ++i) {
             const int e = la[i];
             const int eb = d.out_off[e], en = d.out_off[e + 1];
-            const int lo = stats_edge_lower(l.so_rel, eb, en, rel), hi = stats_edge_lower(l.so_rel, lo, en, rel + 1);
+            const int lo = lower_bound_i(l.so_rel, eb, en, rel), hi = lower_bound_i(l.so_rel, lo, en, rel + 1);
             for (int q = lo + lane; q < hi; q += 64) {
               const int y = l.so_dst[q];
               if (stamp_swap<SMALL>(&stamp[y], s) != s) {
@@ -173,7 +160,7 @@ __global__ __launch_bounds__(SB) void stats_kernel(MinerDev d, MinerLearnDev l, 
                 if (pos < E)
                   lb[pos] = y;
                 else
-                  atomicOr(&a.flags[S_INTERNAL], 1ull);
+                  atomicOr(&a.flags[CTR_INTERNAL], 1ull);
               }
             }
           }
@@ -181,14 +168,14 @@ __global__ __launch_bounds__(SB) void stats_kernel(MinerDev d, MinerLearnDev l, 
           for (int i = lane; i < na; i += 64) {
             const int e = la[i];
             const int en = d.out_off[e + 1];
-            for (int q = stats_edge_lower(l.so_rel, d.out_off[e], en, rel); q < en && l.so_rel[q] == rel; ++q) {
+            for (int q = lower_bound_i(l.so_rel, d.out_off[e], en, rel); q < en && l.so_rel[q] == rel; ++q) {
               const int y = l.so_dst[q];
               if (stamp_swap<SMALL>(&stamp[y], s) != s) {
                 const int pos = atomicAdd(&s_cnt[wid], 1);
                 if (pos < E)
                   lb[pos] = y;
                 else
-                  atomicOr(&a.flags[S_INTERNAL], 1ull);
+                  atomicOr(&a.flags[CTR_INTERNAL], 1ull);
               }
             }
           }
@@ -210,7 +197,7 @@ __global__ __launch_bounds__(SB) void stats_kernel(MinerDev d, MinerLearnDev l, 
           const int rel = l.so_rel[q], y = l.so_dst[q];
           const bool first = q == eb || l.so_rel[q - 1] != rel;
           if (!first && l.so_dst[q - 1] == y) continue;  // a duplicate train edge
-          const int p = stats_edge_lower(a.head_rel, hb, hb + nh, rel);
+          const int p = lower_bound_i(a.head_rel, hb, hb + nh, rel);
           if (p == hb + nh || a.head_rel[p] != rel) continue;
           const bool hit = stamp_load<SMALL>(&stamp[y]) == s;
           const int slot = p - hb;

@@ -255,6 +255,18 @@ def _check_side(side, what, both=False):
     return side
 
 
+def _side_code(side):
+    """The native RNNL_MINER_TAIL / RNNL_MINER_HEAD of a checked side."""
+    return _native.MINER_HEAD if side == "head" else _native.MINER_TAIL
+
+
+def _known_args(lists):
+    """The native (known_keys, known_offs, known_vals, n_keys) of _DeviceLists, or of None: unfiltered."""
+    if lists is None:
+        return None, None, None, 0
+    return lists.keys.data_ptr(), lists.offs.data_ptr(), lists.vals.data_ptr(), lists.keys.numel()
+
+
 def read_queries_file(file_name, graph, side="tail"):
     """Lines `head<TAB>relation` (open) or `head<TAB>relation<TAB>tail`, in the
     names of the graph's dictionaries -> (n, 3) int64 with t = -1 for the open
@@ -510,23 +522,29 @@ class RuleMiner(object):
         self._order = order
         return order, int(n * portion)
 
-    def _ground(self, order_dev, begin, count, pair_base, stream):
+    def _counted(self, entry, *args):
+        """A native entry that ends in (counters, stream): on the current
+        stream with the miner's counters, which are then read and checked.
+        Returns the first counter, the entries of rnnl_miner_ground_count."""
+        _native.call(entry, self._handle, *args, self._counters.data_ptr(),
+                     torch.cuda.current_stream(self.device).cuda_stream)
+        return self._check_counters()
+
+    def _ground(self, order_dev, begin, count, pair_base):
         """The (triple, rule, destination, count) entries of one chunk, or
         None if they would exceed the byte budget and the chunk can be cut."""
         n_pairs = int(pair_base[-1])
         pb = torch.from_numpy(pair_base).to(self.device)
         pair_off = torch.empty(n_pairs + 1, dtype=torch.int64, device=self.device)
-        _native.call("rnnl_miner_ground_count", self._handle, order_dev.data_ptr(), begin, count, pb.data_ptr(),
-                     n_pairs, pair_off.data_ptr(), self._counters.data_ptr(), stream)
-        total = self._check_counters()
+        total = self._counted("rnnl_miner_ground_count", order_dev.data_ptr(), begin, count, pb.data_ptr(), n_pairs,
+                              pair_off.data_ptr())
         if total * 8 > self.budget_bytes and count > 1 and self.chunk_triples is None:
             return None
         dst = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)
         cnt = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)  # u32 path counts
-        _native.call("rnnl_miner_ground_fill", self._handle, order_dev.data_ptr(), begin, count, pb.data_ptr(),
-                     n_pairs, pair_off.data_ptr(), dst.data_ptr(), cnt.data_ptr(), total,
-                     self._counters.data_ptr(), stream)
-        self._check_counters()  # the chain kernels index by these entries: read them only if they are whole
+        # the chain kernels index by these entries: read them only if they are whole
+        self._counted("rnnl_miner_ground_fill", order_dev.data_ptr(), begin, count, pb.data_ptr(), n_pairs,
+                      pair_off.data_ptr(), dst.data_ptr(), cnt.data_ptr(), total)
         return (begin, count, pb, n_pairs, pair_off, dst, cnt)
 
     def _check_counters(self):
@@ -537,7 +555,7 @@ class RuleMiner(object):
             raise _native.NativeError(_native.RNNL_ERR_INTERNAL, "rule miner: grounding failed (flags %r)" % (c[1:],))
         return int(c[0])
 
-    def _chunks(self, order, n_used, stream):
+    def _chunks(self, order, n_used):
         """Ground positions [0, n_used) of `order` chunk by chunk: whole chunks
         of chunk_triples if that is set, else as many triples as the byte
         budget allows (16 bytes per pair, 8 per entry)."""
@@ -558,7 +576,7 @@ class RuleMiner(object):
             while True:
                 pair_base = np.zeros(count + 1, dtype=np.int64)
                 np.cumsum(nr_of[begin:begin + count], out=pair_base[1:])
-                chunk = self._ground(order_dev, begin, count, pair_base, stream)
+                chunk = self._ground(order_dev, begin, count, pair_base)
                 if chunk is not None:
                     break
                 count = max(1, count // 2)
@@ -578,7 +596,7 @@ class RuleMiner(object):
                                         portion)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            for begin, count, pb, n_pairs, pair_off, dst, cnt, odev in self._chunks(order, n_used, stream):
+            for begin, count, pb, n_pairs, pair_off, dst, cnt, odev in self._chunks(order, n_used):
                 _native.call("rnnl_miner_learn", self._handle, odev.data_ptr(), begin, count, pb.data_ptr(), n_pairs,
                              pair_off.data_ptr(), dst.data_ptr(), cnt.data_ptr(), float(lr), float(wd), float(temp),
                              int(bool(fast)), stream)
@@ -590,7 +608,7 @@ class RuleMiner(object):
         order, n_used = self._use_order(order, portion)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            for begin, count, pb, n_pairs, pair_off, dst, cnt, odev in self._chunks(order, n_used, stream):
+            for begin, count, pb, n_pairs, pair_off, dst, cnt, odev in self._chunks(order, n_used):
                 _native.call("rnnl_miner_h_score", self._handle, odev.data_ptr(), begin, count, pb.data_ptr(),
                              n_pairs, pair_off.data_ptr(), dst.data_ptr(), cnt.data_ptr(), int(top_k),
                              float(H_temperature), float(prior_weight), stream)
@@ -780,14 +798,9 @@ class RuleMiner(object):
             qd = torch.from_numpy(q).to(self.device)
             ranks = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
             val = torch.zeros((n, E), dtype=torch.float64, device=self.device) if want_val else None
-            k = self._known_side(side) if filtered else None
-            _native.call("rnnl_miner_evaluate_side", self._handle,
-                         _native.MINER_HEAD if side == "head" else _native.MINER_TAIL, qd.data_ptr(), n,
-                         k.keys.data_ptr() if k else None, k.offs.data_ptr() if k else None,
-                         k.vals.data_ptr() if k else None, k.keys.numel() if k else 0, ranks.data_ptr(),
-                         val.data_ptr() if want_val else None, self._counters.data_ptr(),
-                         torch.cuda.current_stream(self.device).cuda_stream)
-            self._check_counters()
+            known = self._known_side(side) if filtered else None
+            self._counted("rnnl_miner_evaluate_side", _side_code(side), qd.data_ptr(), n, *_known_args(known),
+                          ranks.data_ptr(), val.data_ptr() if want_val else None)
         return ranks, val
 
     def scores(self, triples, side="tail"):
@@ -831,19 +844,19 @@ class RuleMiner(object):
             if q.ndim != 2 or q.shape[1] != 3:
                 raise ValueError("head-side queries must be (n, 3) (h, r, t), h = -1: an open query (got shape %r)"
                                  % (q.shape,))
-            E, R = self.graph.entity_size, self.graph.relation_size
-            if len(q) and (q[:, 1:].min() < 0 or q[:, 2].max() >= E or q[:, 1].max() >= R or q[:, 0].min() < -1
-                           or q[:, 0].max() >= E):
-                raise ValueError("query out of range (h, t in [0, %d), r in [0, %d); h = -1: an open query)" % (E, R))
-            return np.ascontiguousarray(q, dtype=np.int32)
-        if q.ndim != 2 or q.shape[1] not in (2, 3):
-            raise ValueError("queries must be (n, 2) (h, r) or (n, 3) (h, r, t) (got shape %r)" % (q.shape,))
-        if q.shape[1] == 2:
-            q = np.concatenate([q, np.full((len(q), 1), -1, dtype=np.int64)], 1)
+            ans, name = 0, "h"  # the answer's column, the one that may be -1; the other end is the anchor
+        else:
+            if q.ndim != 2 or q.shape[1] not in (2, 3):
+                raise ValueError("queries must be (n, 2) (h, r) or (n, 3) (h, r, t) (got shape %r)" % (q.shape,))
+            if q.shape[1] == 2:
+                q = np.concatenate([q, np.full((len(q), 1), -1, dtype=np.int64)], 1)
+            ans, name = 2, "t"
+        anchor = 2 - ans
         E, R = self.graph.entity_size, self.graph.relation_size
-        if len(q) and (q[:, :2].min() < 0 or q[:, 0].max() >= E or q[:, 1].max() >= R or q[:, 2].min() < -1
-                       or q[:, 2].max() >= E):
-            raise ValueError("query out of range (h, t in [0, %d), r in [0, %d); t = -1: an open query)" % (E, R))
+        if len(q) and (q[:, 1].min() < 0 or q[:, anchor].min() < 0 or q[:, ans].min() < -1
+                       or q[:, anchor].max() >= E or q[:, ans].max() >= E or q[:, 1].max() >= R):
+            raise ValueError("query out of range (h, t in [0, %d), r in [0, %d); %s = -1: an open query)"
+                             % (E, R, name))
         return np.ascontiguousarray(q, dtype=np.int32)
 
     @torch.no_grad()
@@ -875,15 +888,10 @@ class RuleMiner(object):
             score = torch.empty((n, k), dtype=torch.float64, device=self.device)
             valid = torch.empty(n, dtype=torch.int32, device=self.device)
             position = torch.empty(n, dtype=torch.int32, device=self.device)
-            kn = self._known_side(side) if filtered else None
-            _native.call("rnnl_miner_predict_side", self._handle,
-                         _native.MINER_HEAD if side == "head" else _native.MINER_TAIL, qd.data_ptr(), n,
-                         kn.keys.data_ptr() if kn else None, kn.offs.data_ptr() if kn else None,
-                         kn.vals.data_ptr() if kn else None, kn.keys.numel() if kn else 0, k,
-                         _native.MINER_ALL if candidates == "all" else _native.MINER_REACHED, index.data_ptr(),
-                         score.data_ptr(), valid.data_ptr(), position.data_ptr(), self._counters.data_ptr(),
-                         torch.cuda.current_stream(self.device).cuda_stream)
-            self._check_counters()
+            known = self._known_side(side) if filtered else None
+            self._counted("rnnl_miner_predict_side", _side_code(side), qd.data_ptr(), n, *_known_args(known), k,
+                          _native.MINER_ALL if candidates == "all" else _native.MINER_REACHED, index.data_ptr(),
+                          score.data_ptr(), valid.data_ptr(), position.data_ptr())
         return index, score, valid, position
 
     @torch.no_grad()
@@ -913,11 +921,8 @@ class RuleMiner(object):
             total = torch.empty((n, m), dtype=torch.float64, device=self.device)
             rule = torch.empty((n, m, c), dtype=torch.int32, device=self.device)
             count = torch.empty((n, m, c), dtype=torch.int64, device=self.device)
-            _native.call("rnnl_miner_explain_side", self._handle,
-                         _native.MINER_HEAD if side == "head" else _native.MINER_TAIL, qd.data_ptr(), n,
-                         idx.data_ptr(), m, c, fired.data_ptr(), total.data_ptr(), rule.data_ptr(), count.data_ptr(),
-                         self._counters.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-            self._check_counters()
+            self._counted("rnnl_miner_explain_side", _side_code(side), qd.data_ptr(), n, idx.data_ptr(), m, c,
+                          fired.data_ptr(), total.data_ptr(), rule.data_ptr(), count.data_ptr())
         return fired, total, rule, count
 
     def predict(self, split="test", triples=None, k=10, filtered=True, explain=0, rules_per_tail=3,

@@ -230,6 +230,28 @@ def test_path_count_past_32_bits_is_reported(dev):
     assert abs(miner.weights()[0][0] + LR) < 1e-12
 
 
+def test_count_past_32_bits_on_an_inner_hop_that_dead_ends(dev):
+    """Where learn and evaluate differ on purpose.  A chain
+    0 -0-> 1 -1-> 2 -2-> 3 -3-> 4, the first three edges 1,626 times each:
+    1,626^3 = 4,298,942,376 > 2^32 paths reach entity 3, hop 4 carries that
+    count on to entity 4, and no edge of relation 4 leaves entity 4.  The body
+    [0, 1, 2, 3, 4] has no destination.  The query kernels report a count past
+    32 bits on whichever hop carries it; the grounding of learn looks at the
+    final counts only, finds none, and leaves the weight alone."""
+    from rnnlogic_amd import _native
+    from rnnlogic_amd.miner import RuleMiner
+    assert 1626 ** 3 == 4298942376 > 2 ** 32
+    tri = [(0, 0, 1)] * 1626 + [(1, 1, 2)] * 1626 + [(2, 2, 3)] * 1626 + [(3, 3, 4), (0, 5, 5)]
+    miner = RuleMiner(fake_graph(tri, 6, 6), dev, max_body=5)
+    miner.set_logic_rules([[], [], [], [], [], [(5, (0, 1, 2, 3, 4))]])
+    for ask in (miner.scores, miner.eval_ranks):
+        with pytest.raises(_native.NativeError) as err:
+            ask([(0, 5, 5)])
+        assert err.value.code == _native.RNNL_ERR_RANGE
+    miner.learn(LR, WD, TEMP, order=np.arange(len(tri), dtype=np.int32))
+    assert miner.weights()[5][0] == 0.0  # its initial value: no destination, no step
+
+
 # ---------------------------------------------------------- 3. chunking
 def test_chunking_is_bitwise_neutral(dev):
     tri, E, R, rules = many_rules_graph()
