@@ -238,7 +238,7 @@ int rnnl_rules_create(rnnl_graph g, const int32_t *tok, const int64_t *ptr, int3
   // leaves per head (nodes where rules end), in node-id order
   const int n_nodes_total = (int)node_rel.size();
   std::vector<int32_t> head_leaf_ptr(R + 1, 0), head_leaf_node, node_leaf(n_nodes_total, -1);
-  int max_leaves = 0, max_head_nodes = 0;
+  int max_leaves = 0, max_head_nodes = 0, max_head_slots = 0;
   for (int r = 0; r < R; ++r) {
     head_leaf_ptr[r] = (int32_t)head_leaf_node.size();
     if (head_root[r] >= 0) {
@@ -250,6 +250,7 @@ int rnnl_rules_create(rnnl_graph g, const int32_t *tok, const int64_t *ptr, int3
         }
       max_leaves = std::max(max_leaves, nl);
       max_head_nodes = std::max(max_head_nodes, head_nodes[r]);
+      max_head_slots = std::max(max_head_slots, head_nodes[r] - (node_nrules[head_root[r]] == 0 ? 1 : 0));
     }
   }
   head_leaf_ptr[R] = (int32_t)head_leaf_node.size();
@@ -275,6 +276,7 @@ int rnnl_rules_create(rnnl_graph g, const int32_t *tok, const int64_t *ptr, int3
   rs->level_ptr = level_ptr;
   rs->d.max_leaves = max_leaves;
   rs->d.max_head_nodes = max_head_nodes;
+  rs->max_head_slots = max_head_slots;
   std::vector<int32_t> node_info(4 * node_rel.size());
   for (size_t n = 0; n < node_rel.size(); ++n) {
     node_info[4 * n] = node_rel[n];

@@ -138,6 +138,9 @@ struct rnnl_rules_s {
   std::vector<int32_t> level_ptr;     // host: max_depth + 2 offsets into d.level_nodes
   std::vector<int32_t> head_root;     // host copy of d.head_root (R)
   std::vector<int32_t> head_nodes;    // host copy of d.head_nodes (R)
+  // the largest head trie without its root where no rule ends there (an empty
+  // body): the nodes that can hold a grounding entry (predictor.hip's LDS tables)
+  int32_t max_head_slots = 0;
 };
 
 #define RNNL_HIP_CHECK(expr)                                                              \

@@ -96,6 +96,11 @@ __global__ __launch_bounds__(BS) void score_linear_kernel(KParams p, const int *
 // Both only depend on the rule's trie node: per row, for every node of the
 // head's trie (local index node - root < ld), pos = count at all_t[q] and
 // tot = sum over candidates.  One workgroup per row; tot is summed in LDS.
+// The LDS table has no slot for a root where no rule ends (lds_skip: the
+// grounding emits no entry there), so a head's 8,192 bodies of a full prefix
+// set fit the 64 KB.
+__device__ __forceinline__ int lds_skip(const KParams &p, int root) { return p.rl.node_nrules[root] == 0 ? 1 : 0; }
+
 __global__ __launch_bounds__(BS) void rule_stats_kernel(KParams p, const int64_t *__restrict__ all_t, int ld,
                                                         long long *__restrict__ pos, long long *__restrict__ tot) {
   extern __shared__ unsigned long long s_tot[];
@@ -103,7 +108,7 @@ __global__ __launch_bounds__(BS) void rule_stats_kernel(KParams p, const int64_t
     const int nc = p.n_cand[q];
     if (nc <= 0) continue;
     const int r = (int)p.all_r[q];
-    const int root = p.rl.head_root[r], nh = min(p.rl.head_nodes[r], ld);
+    const int root = p.rl.head_root[r], lo = lds_skip(p, root), nh = min(p.rl.head_nodes[r], ld) - lo;
     for (int i = threadIdx.x; i < nh; i += BS) s_tot[i] = 0ull;
     __syncthreads();
     const int64_t qb = p.q_base[q];
@@ -115,12 +120,12 @@ __global__ __launch_bounds__(BS) void rule_stats_kernel(KParams p, const int64_t
         const int2 be = p.bent[e];
         const int k = be.x - root;
         const unsigned long long c = (uint32_t)be.y;
-        atomicAdd(&s_tot[k], c);
+        atomicAdd(&s_tot[k - lo], c);
         if (t == tq) pos[(int64_t)q * ld + k] += (long long)c;  // one lane owns the true tail
       }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < nh; i += BS) tot[(int64_t)q * ld + i] = (long long)s_tot[i];
+    for (int i = threadIdx.x; i < nh; i += BS) tot[(int64_t)q * ld + lo + i] = (long long)s_tot[i];
     __syncthreads();
   }
 }
@@ -187,7 +192,7 @@ __global__ __launch_bounds__(BS) void predictor_backward_kernel(KParams p, const
     const int nc = p.n_cand[q];
     if (nc <= 0) continue;
     const int r = (int)p.all_r[q];
-    const int root = p.rl.head_root[r], nh = min(p.rl.head_nodes[r], ld);
+    const int root = p.rl.head_root[r], lo = lds_skip(p, root), nh = min(p.rl.head_nodes[r], ld) - lo;
     for (int i = threadIdx.x; i < nh; i += BS) s_g[i] = 0ull;
     __syncthreads();
     const int64_t qb = p.q_base[q];
@@ -202,18 +207,18 @@ __global__ __launch_bounds__(BS) void predictor_backward_kernel(KParams p, const
       for (int e = cr.y; e < cr.y + cr.z; ++e) {
         const int2 be = p.bent[e];
         if (bad)
-          atomicAdd(reinterpret_cast<double *>(&s_g[be.x - root]), (double)(uint32_t)be.y * g);
+          atomicAdd(reinterpret_cast<double *>(&s_g[be.x - root - lo]), (double)(uint32_t)be.y * g);
         else
-          atomicAdd(&s_g[be.x - root], (unsigned long long)((long long)(uint32_t)be.y * gf));
+          atomicAdd(&s_g[be.x - root - lo], (unsigned long long)((long long)(uint32_t)be.y * gf));
       }
     }
     __syncthreads();
     for (int i = threadIdx.x; i < nh; i += BS) {
       if (s_g[i] == 0ull) continue;
       if (bad)
-        atomicAdd(reinterpret_cast<double *>(&grad_node[root + i]), __longlong_as_double((long long)s_g[i]));
+        atomicAdd(reinterpret_cast<double *>(&grad_node[root + lo + i]), __longlong_as_double((long long)s_g[i]));
       else
-        atomicAdd(&grad_node[root + i], s_g[i]);
+        atomicAdd(&grad_node[root + lo + i], s_g[i]);
     }
     __syncthreads();
   }
@@ -331,14 +336,16 @@ int rnnl_predictor_rule_stats(void *ws, int32_t nq, int32_t scale, const int32_t
     return RNNL_ERR_INVALID;
   }
   if (nq == 0) return RNNL_OK;
-  if ((int64_t)ld * 8 > 64 * 1024) {
-    set_error("rnnl_predictor_rule_stats: head trie too large for the LDS table");
+  if ((int64_t)r->max_head_slots * 8 > 64 * 1024) {
+    set_error("rnnl_predictor_rule_stats: head trie too large for the LDS table (" + std::to_string(r->max_head_slots) +
+              " nodes that rules reach under one head; 8192 fit)");
     return RNNL_ERR_INVALID;
   }
   KParams p = export_params(ws, nq, scale, n_cand);
   p.rl = r->d;
   p.all_r = all_r;
-  hipLaunchKernelGGL(rule_stats_kernel, dim3((unsigned)std::min<int64_t>(nq, 4096)), dim3(BS), (size_t)ld * 8,
+  hipLaunchKernelGGL(rule_stats_kernel, dim3((unsigned)std::min<int64_t>(nq, 4096)), dim3(BS),
+                     (size_t)std::max(r->max_head_slots, 1) * 8,
                      (hipStream_t)stream, p, all_t, ld, reinterpret_cast<long long *>(pos),
                      reinterpret_cast<long long *>(tot));
   RNNL_HIP_CHECK(hipGetLastError());
@@ -354,8 +361,9 @@ int rnnl_predictor_backward(void *ws, int32_t nq, int32_t scale, const int32_t *
     return RNNL_ERR_INVALID;
   }
   if (nq == 0) return RNNL_OK;
-  if ((int64_t)ld * 8 > 64 * 1024) {
-    set_error("rnnl_predictor_backward: head trie too large for the LDS table");
+  if ((int64_t)r->max_head_slots * 8 > 64 * 1024) {
+    set_error("rnnl_predictor_backward: head trie too large for the LDS table (" + std::to_string(r->max_head_slots) +
+              " nodes that rules reach under one head; 8192 fit)");
     return RNNL_ERR_INVALID;
   }
   KParams p = export_params(ws, nq, scale, n_cand);
@@ -366,7 +374,8 @@ int rnnl_predictor_backward(void *ws, int32_t nq, int32_t scale, const int32_t *
   const unsigned nb = (unsigned)std::min<int64_t>(nq, 4096);
   RNNL_HIP_CHECK(hipMemsetAsync(static_cast<unsigned char *>(ws) + 4 * H_BW_MAXG, 0, 16, st));
   hipLaunchKernelGGL(predictor_bw_stats_kernel, dim3(nb), dim3(BS), 0, st, p, grad_score);
-  hipLaunchKernelGGL(predictor_backward_kernel, dim3(nb), dim3(BS), (size_t)ld * 8, st, p, grad_score, ld,
+  hipLaunchKernelGGL(predictor_backward_kernel, dim3(nb), dim3(BS), (size_t)std::max(r->max_head_slots, 1) * 8, st, p,
+                     grad_score, ld,
                      reinterpret_cast<unsigned long long *>(grad_node));
   hipLaunchKernelGGL(predictor_bw_fix_kernel, dim3((unsigned)std::min<int64_t>((r->d.n_nodes + 255) / 256, 1024)),
                      dim3(256), 0, st, p, r->d.n_nodes, reinterpret_cast<unsigned long long *>(grad_node));

@@ -828,8 +828,11 @@ class Predictor(_HipGrounding, torch.nn.Module):
             return zero - float("-inf"), torch.zeros((nq, E), dtype=torch.bool, device=device)
         nr = self.native_rules(device)
         w = self.rule_weights
-        node_w = torch.zeros(nr.n_nodes, device=device, dtype=w.dtype).index_add(0, nr.node_of_rule, w)
-        val = torch.zeros(C, device=device, dtype=w.dtype).index_add(0, ce, count.to(w.dtype) * node_w.index_select(0, node))
+        # the sums in fp64, rounded once to the parameters' type — forward and, through autograd, backward: as
+        # the fused kernels' exact sums, a score or a gradient is off by one rounding, not by one per term
+        node_w = torch.zeros(nr.n_nodes, device=device, dtype=torch.float64).index_add(0, nr.node_of_rule, w.double())
+        val = torch.zeros(C, device=device, dtype=torch.float64).index_add(
+            0, ce, count.to(torch.float64) * node_w.index_select(0, node)).to(w.dtype)
         score = torch.zeros(nq * E, device=device, dtype=w.dtype)
         if nonfinite:
             rels = torch.unique(all_r).tolist()
@@ -933,9 +936,11 @@ class Predictor(_HipGrounding, torch.nn.Module):
         not depend on it)."""
         device = all_h.device
         n = all_h.numel()
-        H = torch.zeros(self.num_rules, device=device)
+        # the rows' softmax and their sum in fp64, rounded once: fp32 atomics add a rule's thousands of rows
+        # one by one, each add rounding at the running sum (4.6e-3 off at 345 after 2,068 rows)
+        H = torch.zeros(self.num_rules, device=device, dtype=torch.float64)
         if n == 0 or self.num_rules == 0:
-            return H
+            return H.float()
         idx, node, ld = self._rule_table(device)
         nr = self.native_rules(device)
         w_all = self.rule_weights.detach()
@@ -946,14 +951,14 @@ class Predictor(_HipGrounding, torch.nn.Module):
             r = r.to(device, torch.int64).contiguous()
             ridx, k = idx[r], node[r]  # (m, Rmax)
             valid = ridx >= 0
-            w = w_all[ridx.clamp(min=0)]
+            w = w_all[ridx.clamp(min=0)].double()
             pos_score = pos.gather(1, k).to(w.dtype) * w
             neg_score = tot.gather(1, k).to(w.dtype) * w / torch.clamp(n_cand.to(w.dtype), min=1).unsqueeze(1)
             sm = torch.softmax((pos_score - neg_score).masked_fill(~valid, float("-inf")), dim=-1)
             has = valid.any(1, keepdim=True)
             sm = torch.where(valid & has, sm, torch.zeros_like(sm))
             H.index_add_(0, ridx.clamp(min=0).reshape(-1), sm.reshape(-1))
-        return H
+        return H.float()
 
 
 def _train_node_records(nr, agg, head, emb, add_w, stream):

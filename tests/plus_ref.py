@@ -48,9 +48,11 @@ CORE = 40                                 # entities of the dense random neighbo
 CORE_EDGES = 44                           # edges per body relation among them
 
 
-def small_graph(root, seed=0):
+def small_graph(root, seed=0, stars=STARS):
     """Writes the dataset (entities.dict, relations.dict, train / valid /
-    test.txt) and rules.txt under `root`/plus_small<seed>; no parallel edges.
+    test.txt) and rules.txt under `root`/plus_small<seed> (another `stars`
+    tuple: plus_small<seed>_s<its sizes>; the random part is drawn before the
+    stars are laid out, so it is the same); no parallel edges.
 
     A <- every body of length 1..3 over the relations 0..8 (819 rules = trie
             nodes) on 40 core entities with 44 random edges per relation.
@@ -77,7 +79,7 @@ def small_graph(root, seed=0):
     facts = {"A": [(h, REL["A"], t) for h, t in pairs(40, 0, CORE)],
              "C": [(h, REL["C"], t) for h, t in pairs(10, 0, CORE)], "B": [], "D": []}
     n = CORE
-    for k in STARS:
+    for k in stars:
         centre, leaves = n, list(range(n + 1, n + 1 + k))
         n += 1 + k
         trip += [(centre, REL["r1"], x) for x in leaves]
@@ -93,8 +95,9 @@ def small_graph(root, seed=0):
     facts["D"] += [(d0, REL["D"], d0 + 3), (d0 + 6, REL["D"], d0 + 9)]
     for k in ("A", "B", "C", "D"):
         trip += facts[k]
-    assert len(set(trip)) == len(trip) and n <= 512
-    d = os.path.join(str(root), "plus_small%d" % seed)
+    assert len(set(trip)) == len(trip) and (n <= 512 or tuple(stars) != STARS)
+    tag = "" if tuple(stars) == STARS else "_s" + "_".join(map(str, stars))
+    d = os.path.join(str(root), "plus_small%d%s" % (seed, tag))
     os.makedirs(d, exist_ok=True)
     with open(os.path.join(d, "entities.dict"), "w") as f:
         f.write("".join("%d\te%d\n" % (i, i) for i in range(n)))

@@ -284,10 +284,11 @@ def test_predictor_train_lookahead_is_bit_identical(overflow):
     trained weights and the logged losses equal those of the one-call forward
     (prefetch_depth 0) — also when lowered workspace capacities make
     prefetched groundings overflow and fall back to the retried path.  The
-    weights are held to a tight tolerance, not bitwise: the backward
-    (predictor_backward_kernel) sums each node's count x gradient with fp64
-    atomics, whose order may differ between two runs, so a node's gradient
-    can differ in its last fp64 bits and, rarely, its fp32 rounding."""
+    weights are held to a tight tolerance, the assertion this test has had
+    since the backward summed with fp64 atomics; predictor_backward_kernel
+    now sums each node's count x gradient in int64 fixed point, whose result
+    does not depend on the order of the adds (tests/test_gpu_em_step.py
+    asserts the same bytes from two runs of one backward)."""
     import io
     import logging
     import random
