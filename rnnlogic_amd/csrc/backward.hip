@@ -19,11 +19,9 @@
 //       per-chunk slot, with the launch's max |dL/dy| and its sum of path
 //       counts (order-independent: a max and an integer sum).
 //   node_accum_kernel     per bucket entry (node n, count k) of a candidate:
-//       G_n += k dL/dy_c, as int64 fixed point at one scale for the launch
-//       (2^s with sum k x max |dL/dy| x 2^s < 2^62): integer sums, so the
-//       result does not depend on the order of the adds — run-to-run bitwise
-//       (G_n is the gradient of the node's un-folded rule-embedding sum
-//       before the Linear).
+//       G_n += k dL/dy_c, int64 fixed point (grad_fix.h: order-free, run-to-run
+//       bitwise).  G_n is the gradient of the node's un-folded rule-embedding
+//       sum before the Linear.
 //   node_grad_kernel      per trie node: dL/dx_rule = W_add^T G_n for each
 //       member rule (the reference's index_select / matmul backward), and
 //       dL/dW_add = sum_n G_n (x) s_n with s_n the node's embedding sum.
@@ -38,6 +36,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fwd.h"
+#include "grad_fix.h"
 
 namespace rnnl {
 
@@ -60,27 +59,10 @@ constexpr int BW_BIG = 24;      // bucket lists longer than this are walked by t
 // batch's head relation.  Many candidates of a batch share a node (a short
 // rule reaches most of them), so per-entry global atomics serialise on a few
 // addresses (2.4 ms per FB15k-237 batch); summed in LDS first, each
-// workgroup writes one partial row.  int64 fixed point (node_accum_kernel):
-// exact integer sums in any order; the trie's breadth-first numbering puts
-// the short (most shared) rule prefixes first, and nodes past the LDS range
-// take int64 HBM atomics.
+// workgroup writes one partial row.  The trie's breadth-first numbering puts
+// the short (most shared) rule prefixes first; nodes past the LDS range take
+// int64 HBM atomics (grad_fix.h).
 constexpr int BW_LDS_NODES = 768;
-// stats words (scratch): u32 max |dL/dy| bits, pad, u64 sum of the path counts
-// of the entries of candidates with a non-zero score gradient
-struct BwStats {
-  unsigned int maxgy, pad;
-  unsigned long long sumk;
-};
-
-// The launch's fixed-point scale: 2^s with sum k x max|dL/dy| x 2^s < 2^62, so
-// every term and every partial sum of count x dL/dy fits int64.  `bad`: a
-// non-finite dL/dy (the gradients are then NaN, as the reference's would be).
-__device__ __forceinline__ int bw_scale(const BwStats *st, bool &bad) {
-  const float mg = __uint_as_float(st->maxgy);
-  bad = st->maxgy >= 0x7f800000u;
-  const double total = (double)st->sumk * (double)mg;
-  return (bad || !(total > 0.0)) ? 0 : 61 - ilogb(total);
-}
 constexpr int NG_GRID = 128;    // node_grad_kernel workgroups (max)
 
 struct BwdLds {
@@ -93,13 +75,6 @@ struct BwdLds {
 };
 
 __device__ __forceinline__ float relu_f(float x) { return x > 0.f ? x : 0.f; }
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // Sum a per-lane value over the block's waves into lane-independent totals:
 // every wave adds its lane values of one field into red[] (BWB floats), the
@@ -123,7 +98,7 @@ __device__ __forceinline__ float block_sum_lane(BwdLds &S, float v) {
 __global__ __launch_bounds__(BWB) void sum_backward_kernel(KParams p, const float *__restrict__ grad,
                                                             double *__restrict__ grel, float *__restrict__ part,
                                                             float *__restrict__ gy_out, int64_t gy_cap,
-                                                            BwStats *__restrict__ stats, int single) {
+                                                            GradStats *__restrict__ stats, int single) {
   __shared__ BwdLds S;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   for (int i = tid; i < 128 * 32; i += BWB) S.w0[i >> 5][i & 31] = p.s0_w[i];
@@ -353,17 +328,7 @@ __global__ __launch_bounds__(BWB) void sum_backward_kernel(KParams p, const floa
     wave_lds_sync();  // the next chunk rewrites the stage
   }
   flush_rel(cur_r);
-  // the launch's max |dL/dy| and sum of path counts: one atomic per wave
-  // (a max and an integer sum: order-independent)
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    my_max = max(my_max, (unsigned int)__shfl_xor((int)my_max, o, 64));
-    my_k += __shfl_xor(my_k, o, 64);
-  }
-  if (lane == 0) {
-    if (my_max) atomicMax(&stats->maxgy, my_max);
-    if (my_k) atomicAdd(&stats->sumk, my_k);
-  }
+  grad_stats_publish(my_max, my_k, 0ull, stats);
   // block partial row: lane-owned fields summed over the waves (fixed order),
   // lane-local fields summed over the lanes, then over the waves
   // field-major partials: field f of this workgroup at part[f * BW_GRID + block]
@@ -401,12 +366,11 @@ __global__ __launch_bounds__(BWB) void sum_backward_kernel(KParams p, const floa
 }
 
 // G_n += k dL/dy_c per bucket entry (node n, count k) of the candidates of
-// the chunk list, as int64 fixed point at the launch's scale (bw_scale):
-// LDS sums for the head's first nl nodes (one int64 partial row per
-// workgroup, summed by node_grad_kernel), int64 HBM atomics past them.
-// Integer adds: the sums do not depend on their order.
+// the chunk list, as int64 fixed point (grad_fix.h): LDS sums for the head's
+// first nl nodes (one int64 partial row per workgroup, summed by
+// node_grad_kernel), int64 HBM atomics past them.
 __global__ __launch_bounds__(BWB) void node_accum_kernel(KParams p, const float *__restrict__ gy, int64_t gy_cap,
-                                                          const BwStats *__restrict__ stats,
+                                                          const GradStats *__restrict__ stats,
                                                           unsigned long long *__restrict__ gnode,
                                                           long long *__restrict__ gpart, int lo, int nl) {
   __shared__ unsigned long long gacc[BW_LDS_NODES * 16];
@@ -414,27 +378,23 @@ __global__ __launch_bounds__(BWB) void node_accum_kernel(KParams p, const float 
   for (int i = tid; i < nl * 16; i += BWB) gacc[i] = 0ull;
   __syncthreads();
   bool bad;
-  const int sc = bw_scale(stats, bad);
+  const int sc = grad_fix_scale(stats, false, bad);
   const unsigned int *hdr = reinterpret_cast<const unsigned int *>(p.ws);
   const long long nchunks = (long long)*reinterpret_cast<const unsigned long long *>(hdr + H_CHUNKS);
   // bad (a non-finite dL/dy): fp64 sums in the same words instead, so that
   // NaN / inf reach exactly the nodes the reference's would
-  // each dL/dy is rounded to the fixed-point grid once and multiplied by the
-  // integer count: a (node, candidate) pair split over several bucket entries
-  // (phase A's raw duplicates, which vary with the LDS hash's insertion order)
-  // then sums to exactly its merged entry's k x fix(dL/dy)
   auto add = [&](const int2 be, const float (&g)[16]) {
     const double k = (double)(uint32_t)be.y;
     const long long ki = (long long)(uint32_t)be.y;
-    const unsigned ln = (unsigned)(be.x - lo);
+    unsigned long long *w0 = node_word(gacc, gnode, be.x, lo, nl, 0);
 #pragma unroll
     for (int d = 0; d < 16; ++d) {
       if (g[d] == 0.f) continue;
-      unsigned long long *w = ln < (unsigned)nl ? &gacc[ln * 16 + d] : &gnode[(int64_t)be.x * 16 + d];
+      unsigned long long *w = w0 + d;
       if (bad)
         atomicAdd(reinterpret_cast<double *>(w), k * (double)g[d]);
       else
-        atomicAdd(w, (unsigned long long)(ki * llrint(ldexp((double)g[d], sc))));
+        atomicAdd(w, (unsigned long long)(ki * to_fix((double)g[d], sc)));
     }
   };
   const long long nw = (long long)gridDim.x * BW_WAVES;
@@ -488,7 +448,7 @@ __global__ __launch_bounds__(BWB) void node_accum_kernel(KParams p, const float 
 __global__ __launch_bounds__(BWB) void node_grad_kernel(RulesDev rl, int lo, int hi,
                                                          const long long *__restrict__ gnode,
                                                          const long long *__restrict__ gpart, int nrow, int nl,
-                                                         const BwStats *__restrict__ stats,
+                                                         const GradStats *__restrict__ stats,
                                                          const float *__restrict__ emb, int ld,
                                                          const float *__restrict__ add_w, float *__restrict__ gemb,
                                                          int gld, float *__restrict__ part) {
@@ -496,7 +456,7 @@ __global__ __launch_bounds__(BWB) void node_grad_kernel(RulesDev rl, int lo, int
   __shared__ float s_red[BW_WAVES][256];
   const int tid = threadIdx.x, d = tid & 15;
   bool bad;
-  const int sc = bw_scale(stats, bad);
+  const int sc = grad_fix_scale(stats, false, bad);
   s_w[tid] = add_w[tid];  // (16 x 16) row-major: y[i] = sum_j W[i][j] f[j]
   __syncthreads();
   float acc[16];  // lane d: sum_n G_n[d] s_n[j]
@@ -512,14 +472,10 @@ __global__ __launch_bounds__(BWB) void node_grad_kernel(RulesDev rl, int lo, int
       long long gi = gnode[(int64_t)n * 16 + d];
       if (gid < (int64_t)nl * 16) {
         long long a[4] = {0, 0, 0, 0};
-        int b = 0;
-        for (; b + 4 <= nrow; b += 4)
-#pragma unroll
-          for (int u = 0; u < 4; ++u) a[u] += gpart[(int64_t)(b + u) * nl * 16 + gid];
-        for (; b < nrow; ++b) a[0] += gpart[(int64_t)b * nl * 16 + gid];
+        sum_partial_rows(gpart, nrow, (int64_t)nl * 16, gid, a);
         gi += (a[0] + a[1]) + (a[2] + a[3]);
       }
-      gn = (float)ldexp((double)gi, -sc);
+      gn = (float)from_fix(gi, sc);
     } else {  // non-finite dL/dy: the fp64 sums of node_accum_kernel's fallback
       double gd = __longlong_as_double(gnode[(int64_t)n * 16 + d]);
       if (gid < (int64_t)nl * 16)
@@ -621,7 +577,7 @@ static BwdLayout bwd_layout(int64_t n_nodes, int64_t R) {
   L.gpart = o;
   o = align256(o + 8 * (int64_t)BW_GRID * BW_LDS_NODES * 16);
   L.stats = o;
-  o = align256(o + (int64_t)sizeof(BwStats));
+  o = align256(o + (int64_t)sizeof(GradStats));
   L.total = o;
   return L;
 }
@@ -669,9 +625,8 @@ int rnnl_predictorplus_backward(rnnl_graph g, rnnl_rules r, const rnnl_predictor
   }
   const int R = g->d.R;
   const BwdLayout B = bwd_layout(r->d.n_nodes, R);
-  const Layout Ly = make_layout(nq, scale, r->d.n_nodes);
   const int64_t gy_cap = gy_chunks(nq, n_cand_total);
-  if (scratch_bytes < (size_t)B.total || ws_bytes < (size_t)Ly.total ||
+  if (scratch_bytes < (size_t)B.total || ws_bytes < (size_t)make_layout(nq, scale, r->d.n_nodes).total ||
       rows_bytes < (size_t)gy_cap * 16 * 64 * sizeof(float)) {
     set_error("rnnl_predictorplus_backward: scratch or workspace too small");
     return RNNL_ERR_INVALID;
@@ -683,56 +638,34 @@ int rnnl_predictorplus_backward(rnnl_graph g, rnnl_rules r, const rnnl_predictor
   float *part = reinterpret_cast<float *>(sb + B.part);
   float *npart = reinterpret_cast<float *>(sb + B.npart);
   long long *gpart = reinterpret_cast<long long *>(sb + B.gpart);
-  BwStats *stats = reinterpret_cast<BwStats *>(sb + B.stats);
+  GradStats *stats = reinterpret_cast<GradStats *>(sb + B.stats);
   float *gy = static_cast<float *>(rows_scratch);
   // the nodes whose gradient can be non-zero: the head's trie (training
   // batches are one relation), else every node
-  int lo = 0, hi = r->d.n_nodes;
-  if (head >= 0) {
-    lo = r->head_root[head];
-    hi = lo < 0 ? 0 : lo + r->head_nodes[head];
-    if (lo < 0) lo = 0;
-  }
+  int lo, hi;
+  head_node_range(r, head, lo, hi);
   RNNL_HIP_CHECK(hipMemsetAsync(gr->emb, 0, sizeof(float) * (size_t)gr->emb_ld * (size_t)r->d.n_rules, st));
   if (hi > lo) RNNL_HIP_CHECK(hipMemsetAsync(gnode + (int64_t)lo * 16, 0, sizeof(long long) * 16 * (size_t)(hi - lo), st));
   RNNL_HIP_CHECK(hipMemsetAsync(grel, 0, sizeof(double) * 16 * (size_t)R, st));
-  RNNL_HIP_CHECK(hipMemsetAsync(stats, 0, sizeof(BwStats), st));
-  KParams p{};
+  RNNL_HIP_CHECK(hipMemsetAsync(stats, 0, sizeof(GradStats), st));
+  KParams p = export_params(ws, nq, scale, n_cand);
+  set_score_params(p, pp, nullptr, nullptr, nullptr);
   p.g = g->d;
   p.rl = r->d;
-  p.agg = RNNL_AGG_SUM;
-  p.node_w = static_cast<const unsigned char *>(pp->node_w);
-  p.add_w = pp->add_w;
-  p.add_b = pp->add_b;
-  p.ln_w = pp->ln_w;
-  p.ln_b = pp->ln_b;
-  p.s0_w = pp->s0_w;
-  p.s0_b = pp->s0_b;
-  p.s1_w = pp->s1_w;
-  p.s1_b = pp->s1_b;
-  p.rel_emb = pp->rel_emb;
   p.all_r = all_r;
-  p.nq = nq;
-  p.n_cand = const_cast<int32_t *>(n_cand);
-  p.ws = static_cast<unsigned char *>(ws);
-  unsigned char *base = static_cast<unsigned char *>(ws);
-  p.q_base = reinterpret_cast<int64_t *>(base + Ly.off_qbase);
-  p.cand = reinterpret_cast<int4 *>(base + Ly.off_cand);
-  p.bent = reinterpret_cast<int2 *>(base + Ly.off_bent);
-  p.chunks = reinterpret_cast<int2 *>(base + Ly.off_chunk);
   // grid: about one chunk per wave (the chunks: <= n_cand_total / 64 + one
   // per row), at most BW_GRID workgroups
   const int64_t nchunk = n_cand_total / 64 + nq;
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(BW_GRID, (nchunk + BW_WAVES - 1) / BW_WAVES));
-  const int nl = head >= 0 ? std::min(std::max(hi - lo, 0), BW_LDS_NODES) : 0;
+  const int nl = head >= 0 ? std::min(hi - lo, BW_LDS_NODES) : 0;
   hipLaunchKernelGGL(sum_backward_kernel, dim3(grid), dim3(BWB), 0, st, p, grad_score, grel, part, gy, gy_cap, stats,
                      head >= 0 ? 1 : 0);
   hipLaunchKernelGGL(node_accum_kernel, dim3(grid), dim3(BWB), 0, st, p, (const float *)gy, gy_cap,
-                     (const BwStats *)stats, gnode, gpart, lo, nl);
-  const int64_t nthreads = (int64_t)std::max(hi - lo, 0) * 16;
+                     (const GradStats *)stats, gnode, gpart, lo, nl);
+  const int64_t nthreads = (int64_t)(hi - lo) * 16;
   const int ngrid = (int)std::max<int64_t>(1, std::min<int64_t>(NG_GRID, (nthreads + BWB - 1) / BWB));
-  hipLaunchKernelGGL(node_grad_kernel, dim3(ngrid), dim3(BWB), 0, st, r->d, lo, std::max(hi, lo),
-                     (const long long *)gnode, (const long long *)gpart, grid, nl, (const BwStats *)stats, emb, ld,
+  hipLaunchKernelGGL(node_grad_kernel, dim3(ngrid), dim3(BWB), 0, st, r->d, lo, hi,
+                     (const long long *)gnode, (const long long *)gpart, grid, nl, (const GradStats *)stats, emb, ld,
                      pp->add_w, gr->emb, gr->emb_ld, npart);
   const int nwaves = PB_N + 256 + (R * 16 + 63) / 64;  // one wave per field (relation_emb: per 64 entries)
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((nwaves + BW_WAVES - 1) / BW_WAVES), dim3(BWB), 0, st, part, grid,

@@ -54,7 +54,9 @@ constexpr int sort_words(int G) { return (9 * G * 4 / 6) & ~(G - 1); }
 enum {
   H_STATUS = 0, H_DEQUEUE = 1, H_FLAGS = 2, H_ERRBITS = 3, H_ERRQ = 4, H_DEQUEUE2 = 5, H_CHUNKS = 6, H_NCAND = 8,
   H_NENT = 10,  // 64-bit: bucket entries written (<= the pool reserved: duplicates merge in phase B)
-  H_BW_MAXG = 20, H_BW_SUMK = 22  // EM Predictor backward's fixed-point stats (past the status read-back)
+  // EM Predictor backward's GradStats (grad_fix.h), 24 bytes: words 20-25.  Nothing else uses a word past 17 of
+  // the HDR_WORDS_BYTES / 4 = 64 (the status read-back copies words 0-17; the packed weights start at word 64).
+  H_BW_MAXG = 20
 };
 // H_FLAGS bit 0: the launch's rows hold more than one relation (the
 // reference forward's one-relation-per-batch check, predictors.py:54-55 /

@@ -24,6 +24,7 @@
 #include <string>
 
 #include "fwd.h"
+#include "grad_fix.h"
 #include "hostside.h"
 
 namespace rnnl {
@@ -1346,7 +1347,7 @@ bool bad_params(const rnnl_predictor_params *pp, const float *score) {
   return !pp || !score || !pp->node_w || (pp->aggregator != RNNL_AGG_SUM && pp->aggregator != RNNL_AGG_PNA);
 }
 
-// Only the workspace carve-up is needed to read the pool back.
+// Only the workspace carve-up is needed to read the pool and the chunk list back.
 KParams export_params(void *ws, int32_t nq, int32_t scale, const int32_t *n_cand) {
   const Layout Ly = make_layout(nq, scale);
   unsigned char *base = static_cast<unsigned char *>(ws);
@@ -1357,6 +1358,7 @@ KParams export_params(void *ws, int32_t nq, int32_t scale, const int32_t *n_cand
   p.q_base = reinterpret_cast<int64_t *>(base + Ly.off_qbase);
   p.cand = reinterpret_cast<int4 *>(base + Ly.off_cand);
   p.bent = reinterpret_cast<int2 *>(base + Ly.off_bent);
+  p.chunks = reinterpret_cast<int2 *>(base + Ly.off_chunk);  // (the offset does not depend on make_layout's n_nodes)
   return p;
 }
 
@@ -1416,9 +1418,9 @@ int rnnl_node_weights_head(rnnl_rules r, int32_t head, const float *emb, int32_t
     set_error("rnnl_node_weights_head: bad arguments");
     return RNNL_ERR_INVALID;
   }
-  const int lo = r->head_root[head];
-  return node_weights_range("rnnl_node_weights_head", r, lo < 0 ? 0 : lo, lo < 0 ? 0 : r->head_nodes[head], emb, ld,
-                            agg, add_w, node_w, stream);
+  int lo, hi;
+  head_node_range(r, head, lo, hi);
+  return node_weights_range("rnnl_node_weights_head", r, lo, hi - lo, emb, ld, agg, add_w, node_w, stream);
 }
 
 int rnnl_node_weights_size(rnnl_rules r, int32_t agg, size_t *bytes) {

@@ -36,6 +36,7 @@
 
 #include <algorithm>
 
+#include "grad_fix.h"  // wave_sum, wave_max
 #include "internal.h"
 
 namespace rnnl {
@@ -97,18 +98,6 @@ __global__ __launch_bounds__(256) void kge_sample_kernel(
 }
 
 // ------------------------------------------------------------- reductions
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // Sum / max over the block in a fixed order (the same value in every thread).
 // red: kKgeRedSlots floats of LDS; two barriers.
 template <bool MAX>

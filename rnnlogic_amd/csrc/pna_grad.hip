@@ -20,27 +20,22 @@
 //       wsq, and each candidate's min / max gradient to one node tied at the
 //       min / max (the smallest; the reference's dense .min(1) / .max(1)
 //       route it to one index), split evenly among that node's tied rules —
-//       all int64 fixed point at one scale per launch, each gradient rounded
-//       to it once per candidate, so the sums depend neither on the order of
-//       the adds nor on how a (node, candidate) pair is split over bucket
-//       entries; then per rule dL/dx = G1 + 2 x G2 + its min / max shares.
+//       all int64 fixed point (grad_fix.h: order-free, and the same however a
+//       (node, candidate) pair is split over bucket entries); then per rule
+//       dL/dx = G1 + 2 x G2 + its min / max shares.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <string>
 
 #include "fwd.h"
+#include "grad_fix.h"
 
 namespace rnnl {
 
 constexpr int PG_BS = 256;
 constexpr int PG_LDS_NODES = 96;  // the head's first nodes summed in LDS (4 tables: 48 KB)
 constexpr int PG_GRID = 240;      // accumulation workgroups (one partial row block each)
-
-struct PnaGradStats {
-  unsigned int maxg, pad;
-  unsigned long long sumk, ncand;
-};
 
 __device__ __forceinline__ const unsigned int *pna_trailer(const KParams &p, const unsigned char *node_w) {
   return reinterpret_cast<const unsigned int *>(node_w + (int64_t)p.rl.n_nodes * kStridePna);
@@ -145,7 +140,7 @@ __global__ __launch_bounds__(PG_BS) void pna_grad_stats_kernel(KParams p, const 
                                                                 const float *__restrict__ g1,
                                                                 const float *__restrict__ g2,
                                                                 const float *__restrict__ g3,
-                                                                PnaGradStats *__restrict__ st) {
+                                                                GradStats *__restrict__ st) {
   unsigned int m = 0u;
   unsigned long long k = 0ull, n = 0ull;
   for (int64_t c = (int64_t)blockIdx.x * PG_BS + threadIdx.x; c < C; c += (int64_t)gridDim.x * PG_BS) {
@@ -161,38 +156,12 @@ __global__ __launch_bounds__(PG_BS) void pna_grad_stats_kernel(KParams p, const 
     for (int e = cr.y; e < cr.y + cr.z; ++e) k += (uint32_t)p.bent[e].y;
     ++n;
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    m = max(m, (unsigned int)__shfl_xor((int)m, o, 64));
-    k += __shfl_xor(k, o, 64);
-    n += __shfl_xor(n, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (m) atomicMax(&st->maxg, m);
-    if (k) atomicAdd(&st->sumk, k);
-    if (n) atomicAdd(&st->ncand, n);
-  }
-}
-
-// 2^s with (sum count + candidates) x max |gradient| x 2^s < 2^62: every
-// accumulator's total (count x dL/dwsum over entries, or a candidate's whole
-// min / max gradient) fits int64.  bad: a non-finite gradient.
-__device__ __forceinline__ int pna_grad_scale(const PnaGradStats *st, bool &bad) {
-  bad = st->maxg >= 0x7f800000u;
-  const double total = ((double)st->sumk + (double)st->ncand) * (double)__uint_as_float(st->maxg);
-  return (bad || !(total > 0.0)) ? 0 : 61 - ilogb(total);
-}
-
-__device__ __forceinline__ unsigned long long pg_fix(double v, int sc) {
-  return (unsigned long long)llrint(ldexp(v, sc));
+  grad_stats_publish(m, k, n, st);
 }
 
 // One wave per candidate (grid-stride over the C candidates), lane = (entry
 // slot j, dim d) as pna_features_kernel: per bucket entry (node n, count k)
-// G1[n] += k fix(dL/dwsum), G2[n] += k fix(dL/dwsq) — each gradient on the
-// fixed-point grid once, times the integer count, so a (node, candidate) pair
-// split over several bucket entries (phase A's raw duplicates, which vary
-// with its LDS hash's insertion order) sums exactly as its merged entry — and
+// G1[n] += k fix(dL/dwsum), G2[n] += k fix(dL/dwsq) (grad_fix.h), and
 // the candidate's min / max gradient whole to the smallest trie node among
 // its entries tied at the min / max (the reference's dense .min(1) / .max(1)
 // route it to one index, layers.py:100-101; a node's duplicate entries tie
@@ -207,19 +176,21 @@ __global__ __launch_bounds__(PG_BS) void pna_grad_nodes_kernel(
     KParams p, const unsigned char *__restrict__ node_w, const int64_t *__restrict__ cand_off, int64_t C,
     const float *__restrict__ mn, const float *__restrict__ mx, const float *__restrict__ d_wsum,
     const float *__restrict__ d_wsq, const float *__restrict__ d_mn, const float *__restrict__ d_mx,
-    const PnaGradStats *__restrict__ st, int lo, int nl, unsigned long long *__restrict__ G,
+    const GradStats *__restrict__ st, int lo, int nl, unsigned long long *__restrict__ G,
     long long *__restrict__ gpart, int64_t tab) {
   __shared__ unsigned long long s[4][PG_LDS_NODES * 16];  // G1 | G2 | Gmin | Gmax of nodes lo .. lo + nl
   bool bad;
-  const int sc = pna_grad_scale(st, bad);
+  const int sc = grad_fix_scale(st, true, bad);
   for (int i = threadIdx.x; i < nl * 16; i += PG_BS) s[0][i] = s[1][i] = s[2][i] = s[3][i] = 0ull;
   __syncthreads();
-  auto add = [&](int k, int n, int d, unsigned long long v) {
+  // node_word's choice as a branch: its one pointer is generic and would turn
+  // these into flat atomics; the LDS and the global add stay what they were
+  auto add = [&](int k, int n, int d, long long v) {
     const unsigned ln = (unsigned)(n - lo);
     if (ln < (unsigned)nl)
-      atomicAdd(&s[k][ln * 16 + d], v);
+      atomicAdd(&s[k][ln * 16 + d], (unsigned long long)v);
     else
-      atomicAdd(&G[k * tab + (int64_t)n * 16 + d], v);
+      atomicAdd(&G[k * tab + (int64_t)n * 16 + d], (unsigned long long)v);
   };
   const int lane = threadIdx.x & 63, d = lane & 15, j = lane >> 4;
   const int64_t nw = (int64_t)gridDim.x * (PG_BS / 64);
@@ -227,8 +198,8 @@ __global__ __launch_bounds__(PG_BS) void pna_grad_nodes_kernel(
     for (int64_t c = (int64_t)blockIdx.x * (PG_BS / 64) + (threadIdx.x >> 6); c < C; c += nw) {
       const int q = cand_row(cand_off, p.nq, c);
       const int4 cr = p.cand[p.q_base[q] + (c - cand_off[q])];
-      const long long f1 = (long long)pg_fix((double)d_wsum[c * 16 + d], sc);
-      const long long f2 = (long long)pg_fix((double)d_wsq[c * 16 + d], sc);
+      const long long f1 = to_fix((double)d_wsum[c * 16 + d], sc);
+      const long long f2 = to_fix((double)d_wsq[c * 16 + d], sc);
       const float vmn = mn[c * 16 + d], vmx = mx[c * 16 + d];
       int nmn = INT_MAX, nmx = INT_MAX;  // the smallest node tied at the candidate's min / max (dim d)
 #pragma unroll 1
@@ -238,8 +209,8 @@ __global__ __launch_bounds__(PG_BS) void pna_grad_nodes_kernel(
         const long long k = (long long)(uint32_t)be.y;
         if (fr[d] == vmn) nmn = min(nmn, be.x);
         if (fr[16 + d] == vmx) nmx = min(nmx, be.x);
-        if (f1) add(0, be.x, d, (unsigned long long)(k * f1));
-        if (f2) add(1, be.x, d, (unsigned long long)(k * f2));
+        if (f1) add(0, be.x, d, k * f1);
+        if (f2) add(1, be.x, d, k * f2);
       }
       nmn = min(nmn, __shfl_xor(nmn, 16, 64));
       nmn = min(nmn, __shfl_xor(nmn, 32, 64));
@@ -247,8 +218,8 @@ __global__ __launch_bounds__(PG_BS) void pna_grad_nodes_kernel(
       nmx = min(nmx, __shfl_xor(nmx, 32, 64));
       if (j == 0) {
         const float gmn = d_mn[c * 16 + d], gmx = d_mx[c * 16 + d];
-        if (gmn != 0.f && nmn != INT_MAX) add(2, nmn, d, pg_fix((double)gmn, sc));
-        if (gmx != 0.f && nmx != INT_MAX) add(3, nmx, d, pg_fix((double)gmx, sc));
+        if (gmn != 0.f && nmn != INT_MAX) add(2, nmn, d, to_fix((double)gmn, sc));
+        if (gmx != 0.f && nmx != INT_MAX) add(3, nmx, d, to_fix((double)gmx, sc));
       }
     }
   __syncthreads();
@@ -267,12 +238,12 @@ __global__ __launch_bounds__(PG_BS) void pna_grad_nodes_kernel(
 __global__ __launch_bounds__(PG_BS) void pna_grad_rules_kernel(RulesDev rl, int lo, int hi,
                                                                 const unsigned char *__restrict__ node_w,
                                                                 const float *__restrict__ x, int ld,
-                                                                const PnaGradStats *__restrict__ st,
+                                                                const GradStats *__restrict__ st,
                                                                 const long long *__restrict__ G, int64_t tab,
                                                                 const long long *__restrict__ gpart, int nrow,
                                                                 int nl, float *__restrict__ d_x) {
   bool bad;
-  const int sc = pna_grad_scale(st, bad);
+  const int sc = grad_fix_scale(st, true, bad);
   const int64_t total = (int64_t)(hi - lo) * 16;
   for (int64_t gid = (int64_t)blockIdx.x * PG_BS + threadIdx.x; gid < total; gid += (int64_t)gridDim.x * PG_BS) {
     const int n = lo + (int)(gid >> 4), d = (int)(gid & 15);
@@ -281,10 +252,7 @@ __global__ __launch_bounds__(PG_BS) void pna_grad_rules_kernel(RulesDev rl, int 
     long long g[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) g[k] = G[k * tab + (int64_t)n * 16 + d];
-    if (gid < (int64_t)nl * 16)
-      for (int b = 0; b < nrow; ++b)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) g[k] += gpart[((int64_t)b * 4 + k) * nl * 16 + gid];
+    if (gid < (int64_t)nl * 16) sum_partial_rows(gpart, 4 * nrow, (int64_t)nl * 16, gid, g);  // row 4 b + k: table k
     const float *fr = reinterpret_cast<const float *>(node_w + (int64_t)n * kStridePna) + 32;
     const float vmn = fr[d], vmx = fr[16 + d];
     int tmn = 0, tmx = 0;
@@ -293,8 +261,8 @@ __global__ __launch_bounds__(PG_BS) void pna_grad_rules_kernel(RulesDev rl, int 
       tmn += v == vmn;
       tmx += v == vmx;
     }
-    const float f1 = (float)ldexp((double)g[0], -sc), f2 = (float)ldexp((double)g[1], -sc);
-    const float fmn = (float)ldexp((double)g[2], -sc), fmx = (float)ldexp((double)g[3], -sc);
+    const float f1 = (float)from_fix(g[0], sc), f2 = (float)from_fix(g[1], sc);
+    const float fmn = (float)from_fix(g[2], sc), fmx = (float)from_fix(g[3], sc);
     for (int k = kb; k < ke; ++k) {
       const int r = rl.node_rules[k];
       const float v = x[(int64_t)r * ld + d];
@@ -377,18 +345,15 @@ int rnnl_pna_features_backward(rnnl_rules r, const void *node_w, const float *x,
   if (nq == 0 || n_cand_total == 0) return RNNL_OK;
   // the nodes whose gradient can be non-zero: the head's trie (a training
   // batch is one relation; its first nodes summed in LDS), else every node
-  int lo = 0, hi = r->d.n_nodes, nl = 0;
-  if (head >= 0) {
-    lo = std::max(r->head_root[head], 0);
-    hi = r->head_root[head] < 0 ? lo : lo + r->head_nodes[head];
-    nl = std::min(hi - lo, PG_LDS_NODES);
-  }
+  int lo, hi;
+  head_node_range(r, head, lo, hi);
+  const int nl = head >= 0 ? std::min(hi - lo, PG_LDS_NODES) : 0;
   unsigned char *sb = static_cast<unsigned char *>(scratch);
   auto *G = reinterpret_cast<unsigned long long *>(sb);
   for (int k = 0; k < 4; ++k)
     if (hi > lo) RNNL_HIP_CHECK(hipMemsetAsync(G + k * L.tab + (int64_t)lo * 16, 0, (size_t)(hi - lo) * 16 * 8, st));
-  auto *stats = reinterpret_cast<PnaGradStats *>(sb + L.stats);
-  RNNL_HIP_CHECK(hipMemsetAsync(stats, 0, sizeof(PnaGradStats), st));
+  auto *stats = reinterpret_cast<GradStats *>(sb + L.stats);
+  RNNL_HIP_CHECK(hipMemsetAsync(stats, 0, sizeof(GradStats), st));
   KParams p = export_params(ws, nq, scale, n_cand);
   p.rl = r->d;
   p.all_r = all_r;
@@ -398,12 +363,12 @@ int rnnl_pna_features_backward(rnnl_rules r, const void *node_w, const float *x,
   hipLaunchKernelGGL(pna_grad_stats_kernel, dim3(nb), dim3(PG_BS), 0, st, p, cand_off, n_cand_total, d_wsum, d_wsq,
                      d_mn, d_mx, stats);
   hipLaunchKernelGGL(pna_grad_nodes_kernel, dim3(na), dim3(PG_BS), 0, st, p, nw, cand_off, n_cand_total, mn, mx, d_wsum,
-                     d_wsq, d_mn, d_mx, (const PnaGradStats *)stats, lo, nl, G,
+                     d_wsq, d_mn, d_mx, (const GradStats *)stats, lo, nl, G,
                      reinterpret_cast<long long *>(sb + L.gpart), L.tab);
-  const int64_t nthreads = (int64_t)std::max(hi - lo, 0) * 16;
+  const int64_t nthreads = (int64_t)(hi - lo) * 16;
   if (nthreads > 0)
     hipLaunchKernelGGL(pna_grad_rules_kernel, dim3((unsigned)std::min<int64_t>((nthreads + PG_BS - 1) / PG_BS, 4096)),
-                       dim3(PG_BS), 0, st, r->d, lo, hi, nw, x, ld, (const PnaGradStats *)stats,
+                       dim3(PG_BS), 0, st, r->d, lo, hi, nw, x, ld, (const GradStats *)stats,
                        reinterpret_cast<const long long *>(G), L.tab, reinterpret_cast<const long long *>(sb + L.gpart),
                        (int)na, nl, d_x);
   RNNL_HIP_CHECK(hipGetLastError());

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "fwd.h"
+#include "grad_fix.h"
 
 namespace rnnl {
 
@@ -138,9 +139,13 @@ __global__ __launch_bounds__(BS) void rule_stats_kernel(KParams p, const int64_t
 // (one slot per node of the head's trie), then one global atomic per (row,
 // touched node), both int64 fixed point (order-independent).  The caller
 // zero-fills grad_node.
-//
-// The launch's max |grad| at candidates and sum of their entries' path counts
-// (a max and an integer sum: order-independent), for the fixed-point scale.
+
+// The launch's stats words (grad_fix.h) live in the workspace header.
+__device__ __forceinline__ GradStats *bw_stats(const KParams &p) {
+  return reinterpret_cast<GradStats *>(reinterpret_cast<unsigned int *>(p.ws) + H_BW_MAXG);
+}
+
+// The launch's max |grad| at candidates and sum of their entries' path counts.
 __global__ __launch_bounds__(BS) void predictor_bw_stats_kernel(KParams p, const float *__restrict__ grad) {
   unsigned int m = 0u;
   unsigned long long k = 0ull;
@@ -155,39 +160,19 @@ __global__ __launch_bounds__(BS) void predictor_bw_stats_kernel(KParams p, const
       for (int e = cr.y; e < cr.y + cr.z; ++e) k += (uint32_t)p.bent[e].y;
     }
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    m = max(m, (unsigned int)__shfl_xor((int)m, o, 64));
-    k += __shfl_xor(k, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    unsigned int *hdr = reinterpret_cast<unsigned int *>(p.ws);
-    if (m) atomicMax(&hdr[H_BW_MAXG], m);
-    if (k) atomicAdd(reinterpret_cast<unsigned long long *>(hdr + H_BW_SUMK), k);
-  }
-}
-
-// 2^s with sum k x max |grad| x 2^s < 2^62 (bad: a non-finite gradient)
-__device__ __forceinline__ int pred_bw_scale(const KParams &p, bool &bad) {
-  const unsigned int *hdr = reinterpret_cast<const unsigned int *>(p.ws);
-  const unsigned int mb = hdr[H_BW_MAXG];
-  const unsigned long long k = *reinterpret_cast<const unsigned long long *>(hdr + H_BW_SUMK);
-  bad = mb >= 0x7f800000u;
-  const double total = (double)k * (double)__uint_as_float(mb);
-  return (bad || !(total > 0.0)) ? 0 : 61 - ilogb(total);
+  grad_stats_publish(m, k, 0ull, bw_stats(p));
 }
 
 // Per row (one workgroup per query, grid-stride): G_n += count x grad at
 // (row, candidate) for the row's head trie in LDS, then added per node into
-// grad_node — as int64 fixed point at the launch's scale, so the sums do not
-// depend on the order of the adds (run-to-run bitwise); predictor_bw_fix_kernel
-// turns them into fp64.  A non-finite gradient takes fp64 sums instead (NaN /
-// inf reach the nodes the reference's would).
+// grad_node — int64 fixed point (grad_fix.h); predictor_bw_fix_kernel turns the
+// sums into fp64.  A non-finite gradient takes fp64 sums instead (NaN / inf
+// reach the nodes the reference's would).
 __global__ __launch_bounds__(BS) void predictor_backward_kernel(KParams p, const float *__restrict__ grad, int ld,
                                                                 unsigned long long *__restrict__ grad_node) {
   extern __shared__ unsigned long long s_g[];
   bool bad;
-  const int sc = pred_bw_scale(p, bad);
+  const int sc = grad_fix_scale(bw_stats(p), false, bad);
   for (int q = blockIdx.x; q < p.nq; q += gridDim.x) {
     const int nc = p.n_cand[q];
     if (nc <= 0) continue;
@@ -201,9 +186,7 @@ __global__ __launch_bounds__(BS) void predictor_backward_kernel(KParams p, const
       const int4 cr = p.cand[qb + s];
       const double g = (double)gq[cr.x];
       if (g == 0.0) continue;
-      // the gradient on the fixed-point grid once, times each entry's integer
-      // count: split and merged (node, candidate) entries sum alike
-      const long long gf = bad ? 0 : llrint(ldexp(g, sc));
+      const long long gf = bad ? 0 : to_fix(g, sc);
       for (int e = cr.y; e < cr.y + cr.z; ++e) {
         const int2 be = p.bent[e];
         if (bad)
@@ -227,11 +210,11 @@ __global__ __launch_bounds__(BS) void predictor_backward_kernel(KParams p, const
 // grad_node's int64 fixed-point sums -> fp64 in place (the zero fill is 0 in both)
 __global__ void predictor_bw_fix_kernel(KParams p, int n_nodes, unsigned long long *__restrict__ grad_node) {
   bool bad;
-  const int sc = pred_bw_scale(p, bad);
+  const int sc = grad_fix_scale(bw_stats(p), false, bad);
   if (bad) return;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_nodes; i += gridDim.x * blockDim.x) {
     const long long v = (long long)grad_node[i];
-    if (v) reinterpret_cast<double *>(grad_node)[i] = ldexp((double)v, -sc);
+    if (v) reinterpret_cast<double *>(grad_node)[i] = from_fix(v, sc);
   }
 }
 
@@ -372,7 +355,7 @@ int rnnl_predictor_backward(void *ws, int32_t nq, int32_t scale, const int32_t *
   p.g.E = n_entities;
   hipStream_t st = (hipStream_t)stream;
   const unsigned nb = (unsigned)std::min<int64_t>(nq, 4096);
-  RNNL_HIP_CHECK(hipMemsetAsync(static_cast<unsigned char *>(ws) + 4 * H_BW_MAXG, 0, 16, st));
+  RNNL_HIP_CHECK(hipMemsetAsync(static_cast<unsigned char *>(ws) + 4 * H_BW_MAXG, 0, sizeof(GradStats), st));
   hipLaunchKernelGGL(predictor_bw_stats_kernel, dim3(nb), dim3(BS), 0, st, p, grad_score);
   hipLaunchKernelGGL(predictor_backward_kernel, dim3(nb), dim3(BS), (size_t)std::max(r->max_head_slots, 1) * 8, st, p,
                      grad_score, ld,

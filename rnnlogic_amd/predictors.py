@@ -574,6 +574,24 @@ class _RuleGrounder(_HipGrounding):
         return out.index_put_((row[ce], ent[ce]), count, accumulate=True)
 
 
+class _SavedGrounding(object):
+    """The grounding a forward leaves in the model's workspace for its
+    backward: (ws, scale, n_cand) and the workspace's launch count (_ws_touch)
+    at the time."""
+
+    def __init__(self, model, ws, scale, n_cand):
+        self.model, self.ws, self.scale, self.n_cand = model, ws, scale, n_cand
+        self.uses = model._ws_uses.get(ws.data_ptr()) if ws is not None else None
+
+    def get(self, reground):
+        """(ws, scale, n_cand) for the backward; when another launch has used
+        the workspace since the forward, from reground() (the same rows
+        grounded again: the same COO)."""
+        if self.model._ws_uses.get(self.ws.data_ptr()) != self.uses:
+            return reground()
+        return self.ws, self.scale, self.n_cand
+
+
 class _PredictorLinear(torch.autograd.Function):
     """Predictor.forward under autograd (predictors.py:53-80): the HIP forward
     (rnnl_predictor_forward) and its backward (rnnl_predictor_backward: per
@@ -587,13 +605,12 @@ class _PredictorLinear(torch.autograd.Function):
         score, mask, n_cand, ws, scale, n_total = model._forward_launch(all_h, all_r, edges_to_remove,
                                                                         single_relation=True)
         device = score.device
-        ctx.model, ctx.ws, ctx.scale, ctx.n_cand = model, ws, scale, n_cand
+        ctx.model, ctx.grounding = model, _SavedGrounding(model, ws, scale, n_cand)
         # a batch without any candidate returns `mask + bias` in the reference
         # (predictors.py:67-71): the rule weights are not in its graph, so they
         # get no gradient (None, which Adam skips — a zero gradient would still
         # move them through the moment estimates)
         ctx.no_cand = n_total == 0
-        ctx.gen = model._ws_uses.get(ws.data_ptr()) if ws is not None else None
         ctx.rows = model._rows(all_h, all_r, edges_to_remove)[1:]
         ctx.has_bias = bias is not None
         ctx.mark_non_differentiable(mask)
@@ -607,9 +624,7 @@ class _PredictorLinear(torch.autograd.Function):
         nq = all_h.numel()
         gw = gb = None
         if nq and ctx.needs_input_grad[0] and not ctx.no_cand:
-            ws, scale, n_cand = ctx.ws, ctx.scale, ctx.n_cand
-            if model._ws_uses.get(ws.data_ptr()) != ctx.gen:  # the workspace was reused: ground again
-                ws, scale, n_cand = model.ground(all_h, all_r, etr)
+            ws, scale, n_cand = ctx.grounding.get(lambda: model.ground(all_h, all_r, etr))
             nr = model.native_rules(device)
             _, ld = model.head_roots(device)
             g = grad_score.contiguous().float()
@@ -1068,7 +1083,7 @@ class _PlusSumTrain(torch.autograd.Function):
             score.fill_(float("inf"))
         mask = mask8.bool() if mask8 is not None else torch.ones((nq, E), dtype=torch.bool, device=device)
         ctx.model, ctx.kind, ctx.head = model, kind, head
-        ctx.launch = (ws, scale, n_cand, model._ws_uses.get(ws.data_ptr()), node_w, p, emb_d, ws_, bias)
+        ctx.launch = (_SavedGrounding(model, ws, scale, n_cand), node_w, p, emb_d, ws_, bias)
         ctx.rows = (all_h, all_r, etr)
         ctx.mark_non_differentiable(mask)
         return score, mask
@@ -1076,7 +1091,7 @@ class _PlusSumTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_score, grad_mask):
         model, kind = ctx.model, ctx.kind
-        ws, scale, n_cand, gen, node_w, p, emb_d, ws_, bias = ctx.launch
+        grounding, node_w, p, emb_d, ws_, bias = ctx.launch
         all_h, all_r, etr = ctx.rows
         device = all_h.device
         nq, E = all_h.numel(), model.num_entities
@@ -1089,9 +1104,10 @@ class _PlusSumTrain(torch.autograd.Function):
             return (None,) * 7 + (g_base,) + (None,) * 10
         g, nr = model.graph.device_graph(device), model.native_rules(device)
         stream = torch.cuda.current_stream(device).cuda_stream
-        if model._ws_uses.get(ws.data_ptr()) != gen:
-            # another launch reused the workspace since the forward: the same
-            # rows grounded and scored again rebuild the COO and chunk list
+
+        def forward_again():
+            # the same rows grounded and scored again rebuild the COO and the chunk list
+            n_cand = grounding.n_cand
             scratch = torch.empty((nq, E), dtype=torch.float32, device=device)
             _native.call("rnnl_fill_value", 0.0, scratch.numel(), scratch.data_ptr(), stream)
             p2 = _native.PredictorParams.from_buffer_copy(p)
@@ -1101,9 +1117,10 @@ class _PlusSumTrain(torch.autograd.Function):
                 _native.call("rnnl_predictorplus_forward", g, nr.ptr, ctypes.byref(p2), all_h.data_ptr(),
                              all_r.data_ptr(), etr.data_ptr() if etr is not None else None, nq, scratch.data_ptr(),
                              None, n_cand.data_ptr(), None, ws2.data_ptr(), ws2.numel(), scale2, stream)
-            ws, scale = model._launch(device, nq, run)
+            return model._launch(device, nq, run) + (n_cand,)
+        ws, scale, n_cand = grounding.get(forward_again)
         gs = grad_score.float().contiguous()
-        sb = model._backward_scratch(device)
+        sb = model._scratch(device, "bwd", "rnnl_predictorplus_backward_size", model.num_relations)
         nrb = ctypes.c_size_t()
         _native.call("rnnl_predictorplus_backward_rows_size", nq, ctx.n_total, ctypes.byref(nrb))
         rows_sb = torch.empty(max(nrb.value, 4), dtype=torch.uint8, device=device)
@@ -1161,7 +1178,7 @@ class _PnaStats(torch.autograd.Function):
             # the records' / sums' range bits: RNNL_ERR_RANGE -> the caller's COO path
             _native.check(_native.lib().rnnl_forward_status(ws.data_ptr(), stream))
         ctx.model, ctx.head, ctx.C = model, head, C
-        ctx.launch = (ws, scale, n_cand, cand_off, model._ws_uses.get(ws.data_ptr()), node_w, emb_d)
+        ctx.launch = (_SavedGrounding(model, ws, scale, n_cand), cand_off, node_w, emb_d)
         ctx.rows = (all_h, all_r, etr)
         ctx.save_for_backward(mn, mx)
         ctx.mark_non_differentiable(deg, row, ent, row_scale)
@@ -1173,15 +1190,14 @@ class _PnaStats(torch.autograd.Function):
             return (None,) * 6
         model = ctx.model
         mn, mx = ctx.saved_tensors
-        ws, scale, n_cand, cand_off, gen, node_w, emb_d = ctx.launch
+        grounding, cand_off, node_w, emb_d = ctx.launch
         all_h, all_r, etr = ctx.rows
         device = all_h.device
-        if model._ws_uses.get(ws.data_ptr()) != gen:  # the workspace was reused: ground again (same COO)
-            ws, scale, n_cand = model.ground(all_h, all_r, etr)
+        ws, scale, n_cand = grounding.get(lambda: model.ground(all_h, all_r, etr))
         grads = [g.float().contiguous() if g is not None else torch.zeros_like(mn) for g in (g_wsum, g_wsq, g_mn, g_mx)]
         nr = model.native_rules(device)
         d_x = torch.empty((model.num_rules, 16), dtype=torch.float32, device=device)
-        sb = model._pna_scratch(device)
+        sb = model._scratch(device, "pna_bwd", "rnnl_pna_features_backward_scratch")
         _native.call("rnnl_pna_features_backward", nr.ptr, node_w.data_ptr(), emb_d.data_ptr(), 16, ws.data_ptr(),
                      all_h.numel(), scale, all_r.data_ptr(), n_cand.data_ptr(), cand_off.data_ptr(), ctx.C, mn.data_ptr(),
                      mx.data_ptr(), *[g.data_ptr() for g in grads], ctx.head, sb.data_ptr(), sb.numel(),
@@ -1874,12 +1890,14 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         out = self.rule_to_entity.finish(wsum, wsq, mn, mx, deg, row, all_h.numel(), row_scale=row_scale)
         return self._score_tail(all_h, all_r, row, ent, out, head=head)
 
-    def _pna_scratch(self, device):
-        key = ("pna_bwd", self._device_index(device))
+    def _scratch(self, device, key, size_entry, *args):
+        """The device's scratch buffer `key`, of the size the library's
+        size_entry(rules, *args, &bytes) asks for; kept."""
+        key = (key, self._device_index(device))
         sb = self._side.get(key)
         if sb is None:
             n = ctypes.c_size_t()
-            _native.call("rnnl_pna_features_backward_scratch", self.native_rules(device).ptr, ctypes.byref(n))
+            _native.call(size_entry, self.native_rules(device).ptr, *args, ctypes.byref(n))
             sb = self._side[key] = torch.empty(n.value, dtype=torch.uint8, device=device)
         return sb
 
@@ -1892,16 +1910,6 @@ class PredictorPlus(_HipGrounding, torch.nn.Module):
         _native.call("rnnl_predictorplus_ground", g, nr.ptr, _native.AGG_SUM, h.data_ptr(), r.data_ptr(),
                      etr.data_ptr() if etr is not None else None, nq, n_cand.data_ptr(), ws.data_ptr(), ws.numel(),
                      scale, 0, stream)
-
-    def _backward_scratch(self, device):
-        key = ("bwd", self._device_index(device))
-        sb = self._side.get(key)
-        if sb is None:
-            n = ctypes.c_size_t()
-            _native.call("rnnl_predictorplus_backward_size", self.native_rules(device).ptr, self.num_relations,
-                         ctypes.byref(n))
-            sb = self._side[key] = torch.empty(n.value, dtype=torch.uint8, device=device)
-        return sb
 
     @_native.on_input_device
     def forward_coo(self, all_h, all_r, edges_to_remove=None, nonfinite=False):
