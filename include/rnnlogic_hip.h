@@ -809,6 +809,45 @@ int rnnl_miner_explain_side(rnnl_miner m, int32_t side, const int32_t *queries, 
                             int32_t n_slots, int32_t c, int32_t *fired, double *total, int32_t *rule, int64_t *count,
                             uint64_t *counters, void *stream);
 
+/* ------------------------------------------ how a query's rules combine --
+ * rnnl_miner_set_aggregation chooses how rnnl_miner_evaluate*, _predict* and
+ * _explain* form val[e] from relation r's rules k (list order).  fires_k(e):
+ * rule k has at least one path to e (tail side: from h; head side: from e to
+ * t), every edge equal to (h, r, t) skipped on every hop.
+ *   RNNL_MINER_AGG_SUM (the default, and again after rnnl_miner_set_rules*):
+ *     val[e] = sum_k wt[k] * (double)#paths_k(e), as documented above.
+ *   RNNL_MINER_AGG_NOISY_OR: val[e] = sum over the k with fires_k(e) of
+ *     operand[k], plain fp64 adds in list order, no multiply.  With operand[k]
+ *     = -log1p(-w_k) of a confidence w_k in [0, 1] this is -log prod(1 - w_k),
+ *     which ranks as 1 - prod(1 - w_k) does; the probability is -expm1(-val).
+ *   RNNL_MINER_AGG_MAX: operand[k] is the rule's class, an integer 0..131,071
+ *     held as a double (0: the rule contributes nothing; larger = stronger).
+ *     With c1 >= c2 >= c3 the `depth` largest classes among the firing rules,
+ *     counted with multiplicity (two firing rules of one class give c1 = c2),
+ *     0 past `depth` and past the number of firing rules,
+ *       val[e] = (double)(c1 * 2^34 + c2 * 2^17 + c3)
+ *     — three 17-bit fields, an exactly represented integer below 2^51.  Depth
+ *     1 is the plain max; 2 and 3 break its ties by the next strongest firing
+ *     rules.  The key depends on the set of firing rules, not on their order.
+ * In the two new modes the grounding marks reachability, it does not count
+ * paths: counters[1] (RNNL_ERR_RANGE) is never set, and the `count` explain
+ * returns is 1 for every listed rule.  There `total` is the entity's val
+ * bitwise, `fired` as above, and the listed rules are the firing rules with
+ * the largest operand, ties by list index.  val is an ordinary non-negative
+ * double in every mode: ranks, order, ties and "+0.0 = untouched" read as above.
+ *   operand (device, n_rules doubles in list order) is checked by a small
+ *   kernel (finite and >= 0; MAX: an integer <= 131,071; RNNL_ERR_INVALID, the
+ *   handle unchanged) and copied into the handle; ignored, and may be null, for
+ *   SUM.  depth counts for MAX only.  The mode is state of the handle; learn,
+ *   h_score and the statistics never read it.  An unknown agg, or a depth
+ *   outside 1..3 with MAX, is RNNL_ERR_INVALID before the handle is looked at.
+ *   The call synchronises. */
+#define RNNL_MINER_AGG_SUM 0
+#define RNNL_MINER_AGG_NOISY_OR 1 /* val = sum of operand over firing rules */
+#define RNNL_MINER_AGG_MAX 2      /* val = key of the `depth` largest operands (classes) */
+#define RNNL_MINER_AGG_CLASS_MAX 131071
+int rnnl_miner_set_aggregation(rnnl_miner m, int32_t agg, int32_t depth, const double *operand, void *stream);
+
 /* ------------------------------------- support and confidence of rules --
  * The exact counts behind standard and PCA confidence, on the handle's train
  * graph as given: no inverses, and — unlike search, learn and evaluate — no

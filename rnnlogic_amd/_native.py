@@ -24,6 +24,8 @@ KGE_TAIL, KGE_HEAD = 0, 1
 MINER_TOPK_MAX, MINER_EXPLAIN_MAX = 256, 16  # RNNL_MINER_TOPK_MAX, RNNL_MINER_EXPLAIN_MAX
 MINER_REACHED, MINER_ALL = 0, 1
 MINER_TAIL, MINER_HEAD = 0, 1  # RNNL_MINER_TAIL, RNNL_MINER_HEAD
+MINER_AGG_SUM, MINER_AGG_NOISY_OR, MINER_AGG_MAX = 0, 1, 2  # RNNL_MINER_AGG_*
+MINER_AGG_CLASS_MAX = 131071  # RNNL_MINER_AGG_CLASS_MAX: three classes fit 51 bits of a double
 
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -126,6 +128,7 @@ SIGNATURES = [
     ("rnnl_miner_predict_side", ctypes.c_int,
      [_P, _I32, _P, _I64, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     ("rnnl_miner_explain_side", ctypes.c_int, [_P, _I32, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    ("rnnl_miner_set_aggregation", ctypes.c_int, [_P, _I32, _I32, _P, _P]),
     ("rnnl_miner_rule_stats_scratch", ctypes.c_int, [_P, _I64, _I64, _I32, _P]),
     ("rnnl_miner_rule_stats", ctypes.c_int,
      [_P, _I64, _P, _P, _P, _P, _I32, ctypes.c_uint32, _P, ctypes.c_size_t, _P, _P, _P]),

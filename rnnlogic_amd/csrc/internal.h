@@ -51,11 +51,14 @@ struct MinerLearnDev {
   const int32_t *so_rel = nullptr, *so_dst = nullptr;  // n, n
   const int32_t *si_rel = nullptr, *si_src = nullptr;  // n, n
   int32_t n_rules = 0;
+  int32_t agg_depth = 1;               // RNNL_MINER_AGG_MAX: the classes a key keeps, 1..3 (mine_ground.h)
   const int32_t *rule_off = nullptr;   // R + 1: relation r's rules are [rule_off[r], rule_off[r + 1])
   const int32_t *rule_len = nullptr;   // n_rules, 0..RULE_STRIDE
   const int32_t *rule_body = nullptr;  // n_rules x RULE_STRIDE
   const double *prior = nullptr;       // n_rules
   double *wt = nullptr, *am = nullptr, *av = nullptr, *at = nullptr, *H = nullptr, *val = nullptr;  // n_rules
+  // n_rules: the aggregation operand of rnnl_miner_set_aggregation (u_k of noisy-or, the class of max as a double)
+  double *op = nullptr;
 };
 
 // Rule bodies as one prefix trie per head relation.  Node ids are global;
@@ -121,6 +124,8 @@ struct rnnl_miner_s {
   int32_t eval_blocks = 0;
   // rnnl_miner_predict above its LDS regime: per workgroup a list (int) and a flag byte per entity; one of bufs
   unsigned char *pred_flags = nullptr;
+  // how evaluate / predict / explain form val (rnnl_miner_set_aggregation); set_rules puts it back to SUM
+  int32_t agg = 0;
 };
 
 struct rnnl_graph_s {

@@ -86,7 +86,11 @@ struct GroundScratch {
 // end at -1 skips nothing.  wide is set when a frontier count past 32 bits is
 // carried over an edge.  The barriers before and after, the reset of the old
 // frontier and the swap belong to the caller.
-template <bool HEAD>
+// COUNT false (the noisy-or and max aggregations of mine_ground.h, which ask
+// only whether a rule reaches an entity): the dense slots hold 1 where the
+// frontier is, not path counts: the first touch is an integer atomic OR with 1,
+// the append as before; no count is read or carried and wide is never set.
+template <bool HEAD, bool COUNT = true>
 __device__ __forceinline__ void ground_hop(const MinerDev &d, const MinerLearnDev &l, const GroundScratch &s, int na,
                                            int lane, int rel, int h, int r, int t, int *n_next, bool &wide) {
   const int32_t *e_off = HEAD ? d.in_off : d.out_off;   // the edges of an entity on this side,
@@ -94,13 +98,17 @@ __device__ __forceinline__ void ground_hop(const MinerDev &d, const MinerLearnDe
   const int32_t *e_end = HEAD ? l.si_src : l.so_dst;
   for (int i = lane; i < na; i += 64) {
     const int e = s.la[i];
-    const unsigned long long n = ld_u64(&s.ca[e]);
+    const unsigned long long n = COUNT ? ld_u64(&s.ca[e]) : 1ull;
     const int en = e_off[e + 1];
     for (int b = lower_bound_i(e_rel, e_off[e], en, rel); b < en && e_rel[b] == rel; ++b) {
       const int x = e_end[b];
       if (rel == r && (HEAD ? (x == h && e == t) : (e == h && x == t))) continue;
-      wide |= n > 0xffffffffull;  // the paths through here alone are past 32 bits
-      if (atomicAdd(&s.cb[x], n) == 0) s.lb[atomicAdd(n_next, 1)] = x;
+      if (COUNT) {
+        wide |= n > 0xffffffffull;  // the paths through here alone are past 32 bits
+        if (atomicAdd(&s.cb[x], n) == 0) s.lb[atomicAdd(n_next, 1)] = x;
+      } else {
+        if (atomicOr(&s.cb[x], 1ull) == 0) s.lb[atomicAdd(n_next, 1)] = x;
+      }
     }
   }
 }

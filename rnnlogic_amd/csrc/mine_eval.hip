@@ -31,6 +31,12 @@
 // backward from t over the in-edges; h is the answer, the known lists are the
 // known heads of (r, t).  The same kernel with h and t exchanging roles: `anc`
 // is the end the grounding starts at, `ans` the answer's end.
+//
+// The aggregation (rnnl_miner_set_aggregation below): the third
+// template parameter AGG.  AGG_SUM is everything above.  AGG_NOISY_OR and
+// AGG_MAX ground reachability, not counts, and val[e] is the sum of the
+// operands l.op[k] of the rules that reach e, or the key of their largest
+// classes (mine_ground.h); the ranks are taken from val as above.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,7 +56,7 @@ struct EvalArgs {
   unsigned long long *flags;
 };
 
-template <bool SMALL, bool HEAD>
+template <bool SMALL, bool HEAD, int AGG>
 __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, EvalArgs a) {
   __shared__ int s_n[EW], s_na[EW], s_g[EW], s_ge[EW];
   const int E = d.E, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -77,8 +83,8 @@ __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, E
 #pragma unroll 1
     for (int jb = 0; jb < nr; jb += EW) {
       const int nw = min(EW, nr - jb);  // rules of this round
-      eval_ground_round<HEAD>(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
-      eval_round_into_val<false>(l, ints, E, rb, jb, nw, s_na, val, nullptr, nullptr, nullptr, wide);
+      eval_ground_round<HEAD, AGG>(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
+      eval_round_into_val<false, AGG>(l, ints, E, rb, jb, nw, s_na, val, nullptr, nullptr, nullptr, wide);
     }
     if (wide) atomicOr(&a.flags[CTR_RANGE], 1ull);
     __syncthreads();
@@ -124,11 +130,66 @@ __global__ __launch_bounds__(EB) void eval_kernel(MinerDev d, MinerLearnDev l, E
   }
 }
 
+// rnnl_miner_set_aggregation's check of its operand: finite and >= 0; is_max: an integer class <= 131,071
+__global__ void agg_check_kernel(const double *op, int n, int is_max, unsigned int *bad) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const double v = op[i];
+    bool ok = v >= 0.0 && v < INFINITY;  // (false for a NaN)
+    if (ok && is_max) ok = v <= (double)RNNL_MINER_AGG_CLASS_MAX && (double)(unsigned)v == v;
+    if (!ok) atomicOr(bad, 1u);
+  }
+}
+
 }  // namespace rnnl
 
 using namespace rnnl;
 
 extern "C" {
+
+int rnnl_miner_set_aggregation(rnnl_miner m, int32_t agg, int32_t depth, const double *operand, void *stream) {
+  if (agg != RNNL_MINER_AGG_SUM && agg != RNNL_MINER_AGG_NOISY_OR && agg != RNNL_MINER_AGG_MAX) {
+    set_error("rnnl_miner_set_aggregation: agg must be RNNL_MINER_AGG_SUM, _NOISY_OR or _MAX");
+    return RNNL_ERR_INVALID;
+  }
+  if (agg == RNNL_MINER_AGG_MAX && (depth < 1 || depth > 3)) {
+    set_error("rnnl_miner_set_aggregation: depth must be 1..3");
+    return RNNL_ERR_INVALID;
+  }
+  if (!m || !m->l.rule_off || (agg != RNNL_MINER_AGG_SUM && m->l.n_rules > 0 && !operand)) {
+    set_error("rnnl_miner_set_aggregation: bad arguments (set the rules first; an operand per rule)");
+    return RNNL_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int n = m->l.n_rules;
+  if (agg != RNNL_MINER_AGG_SUM && n > 0) {
+    unsigned int *bad = nullptr, host_bad = 0;
+    if (hipMalloc(reinterpret_cast<void **>(&bad), sizeof(unsigned int)) != hipSuccess) {
+      set_error("rnnl_miner_set_aggregation: device allocation failed");
+      return RNNL_ERR_NOMEM;
+    }
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(unsigned int), st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(agg_check_kernel, dim3((unsigned)std::min(1024, (n + 255) / 256)), dim3(256), 0, st, operand,
+                         n, (int)(agg == RNNL_MINER_AGG_MAX), bad);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&host_bad, bad, sizeof(unsigned int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(bad);
+    RNNL_HIP_CHECK(e);
+    if (host_bad) {
+      set_error(agg == RNNL_MINER_AGG_MAX
+                    ? "rnnl_miner_set_aggregation: a class is not an integer in 0..131071"
+                    : "rnnl_miner_set_aggregation: an operand is not finite and >= 0");
+      return RNNL_ERR_INVALID;
+    }
+    RNNL_HIP_CHECK(hipMemcpyAsync(m->l.op, operand, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+    RNNL_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  m->agg = agg;
+  m->l.agg_depth = agg == RNNL_MINER_AGG_MAX ? depth : 1;
+  return RNNL_OK;
+}
 
 int rnnl_miner_set_weights(rnnl_miner m, const double *weights, void *stream) {
   if (!m || !m->l.rule_off || (m->l.n_rules > 0 && !weights)) {
@@ -159,7 +220,9 @@ int rnnl_miner_evaluate_side(rnnl_miner m, int32_t side, const int32_t *queries,
   a.ranks = ranks;
   a.val_out = val;
   return query_launch(m, "rnnl_miner_evaluate", side, n, 0, a, counters, stream,
-                      [](auto small, auto head) { return eval_kernel<decltype(small)::value, decltype(head)::value>; });
+                      [](auto small, auto head, auto agg) {
+                        return eval_kernel<decltype(small)::value, decltype(head)::value, decltype(agg)::value>;
+                      });
 }
 
 int rnnl_miner_evaluate(rnnl_miner m, const int32_t *queries, int64_t n, const int64_t *known_keys,

@@ -14,6 +14,18 @@
 // flag bytes (PRED_PER_E).  Up to EVAL_LDS_E entities all of it lives in LDS,
 // above that in the handle's eval_scratch (and pred_flags), zeroed when
 // allocated and left zeroed by every query.
+//
+// The aggregation (rnnl_miner_set_aggregation) is a template
+// parameter AGG of the kernels, of a round's grounding and of the round into
+// val.  AGG_SUM: path counts, val += wt * count.  AGG_NOISY_OR and AGG_MAX ask
+// only whether a rule reaches an entity: the grounding marks the dense slots
+// with 1 (ground_hop<HEAD, false>), and a destination's val takes the rule's
+// operand l.op[k]: added (noisy-or), or inserted as a 17-bit class into the
+// three-field key val holds (max).  The slots are written at the entities of a
+// frontier list only (the first touch appends), and the resets walk those
+// lists — the old frontier after every hop, the destinations when the round
+// enters val — whatever the slots hold; so the scratch regime's "every query
+// leaves it zeroed" holds in the new modes as it does for counts.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,6 +47,29 @@ constexpr size_t PRED_FLAG_PER_E = 1;                 // and its flag bytes, beh
 constexpr size_t PRED_PER_E = PRED_LIST_PER_E + PRED_FLAG_PER_E;
 constexpr size_t EVAL_SCRATCH = 256u << 20;
 constexpr int EVAL_MAX_BLOCKS = 2048;
+
+enum : int { AGG_SUM = RNNL_MINER_AGG_SUM, AGG_NOISY_OR = RNNL_MINER_AGG_NOISY_OR, AGG_MAX = RNNL_MINER_AGG_MAX };
+
+// AGG_MAX: class a (> 0) of a firing rule enters the key of an entity: the
+// three largest classes so far, with multiplicity, as 17-bit fields c1 c2 c3
+// of an integer held exactly in a double; cut to `depth` fields.
+__device__ __forceinline__ double agg_max_insert(double key, unsigned a, int depth) {
+  const unsigned long long k = (unsigned long long)key;
+  unsigned c1 = (unsigned)(k >> 34), c2 = (unsigned)(k >> 17) & 0x1ffffu, c3 = (unsigned)k & 0x1ffffu;
+  if (a > c1) {
+    c3 = c2;
+    c2 = c1;
+    c1 = a;
+  } else if (a > c2) {
+    c3 = c2;
+    c2 = a;
+  } else if (a > c3) {
+    c3 = a;
+  }
+  if (depth < 3) c3 = 0;
+  if (depth < 2) c2 = 0;
+  return (double)(((unsigned long long)c1 << 34) | ((unsigned long long)c2 << 17) | c3);
+}
 
 // The known answers of (relation, anchor) pairs: keys r * E + anchor ascending,
 // key i's answers vals[offs[i], offs[i + 1]) ascending.  keys == nullptr: none.
@@ -114,8 +149,9 @@ __device__ __forceinline__ void eval_zero_ints(unsigned char *ints, int E) {
 // when any hop carries a count past 32 bits on, whether or not the paths go on
 // to a destination (ground_kernel of mine_learn.hip looks at the final counts
 // only).  Called by the whole workgroup; the waves stay in step, a wave whose
-// rule has ended (act false) only keeps the barriers.
-template <bool HEAD>
+// rule has ended (act false) only keeps the barriers.  AGG other than AGG_SUM:
+// the slots hold 1 where a frontier is, no counts; wide is never set.
+template <bool HEAD, int AGG = AGG_SUM>
 __device__ __forceinline__ void eval_ground_round(const MinerDev &d, const MinerLearnDev &l, unsigned char *ints,
                                                   int h, int r, int t, int rb, int jb, int nw, int *s_n, int *s_na,
                                                   bool &wide) {
@@ -139,7 +175,7 @@ __device__ __forceinline__ void eval_ground_round(const MinerDev &d, const Miner
     if (act && lane == 0) s_n[wid] = 0;
     __syncthreads();
     if (act)
-      ground_hop<HEAD>(d, l, s, na, lane, l.rule_body[RULE_STRIDE * rule + (HEAD ? len - 1 - k : k)], h, r, t,
+      ground_hop<HEAD, AGG == AGG_SUM>(d, l, s, na, lane, l.rule_body[RULE_STRIDE * rule + (HEAD ? len - 1 - k : k)], h, r, t,
                        &s_n[wid], wide);
     __syncthreads();
     if (act) {
@@ -163,22 +199,32 @@ __device__ __forceinline__ GroundScratch eval_final(unsigned char *ints, int E, 
 // reached[x] is set for every destination (a path count > 0, whatever the
 // weight), and a destination reached for the first time is appended to
 // touched[*n_touched] (an LDS counter): the entities whose val was written.
-template <bool REACHED>
+// AGG_NOISY_OR: val[x] + l.op[k] at every destination, no product.  AGG_MAX:
+// the class l.op[k], if > 0, inserted into the key val[x] holds
+// (agg_max_insert); one thread per destination within a rule and the barrier
+// between rules, as for the sum.
+template <bool REACHED, int AGG = AGG_SUM>
 __device__ __forceinline__ void eval_round_into_val(const MinerLearnDev &l, unsigned char *ints, int E, int rb, int jb,
                                                     int nw, const int *s_na, double *val, unsigned char *reached,
                                                     int *touched, int *n_touched, bool &wide) {
   for (int w = 0; w < nw; ++w) {
     const int len2 = l.rule_len[rb + jb + w];
     if (len2 == 0) continue;  // an empty body reaches nothing
-    const double wt = l.wt[rb + jb + w];
+    const double wt = AGG == AGG_SUM ? l.wt[rb + jb + w] : l.op[rb + jb + w];
     const GroundScratch f = eval_final(ints, E, w, len2);
     const int n2 = s_na[w];
     for (int i = threadIdx.x; i < n2; i += EB) {
       const int x = f.la[i];
       const unsigned long long c = ld_u64(&f.ca[x]);
-      wide |= c > 0xffffffffull;
-      const double term = wt * (double)c;
-      val[x] = val[x] + term;
+      if (AGG == AGG_SUM) {
+        wide |= c > 0xffffffffull;
+        const double term = wt * (double)c;
+        val[x] = val[x] + term;
+      } else if (AGG == AGG_NOISY_OR) {
+        val[x] = val[x] + wt;
+      } else if (wt > 0.0) {
+        val[x] = agg_max_insert(val[x], (unsigned)wt, l.agg_depth);
+      }
       if (REACHED && c > 0 && !reached[x]) {  // one thread per x within a rule, a barrier between rules
         reached[x] = 1;
         touched[atomicAdd(n_touched, 1)] = x;
@@ -235,8 +281,8 @@ struct NoPrep {
 // clears the counters; picks the kernel by regime (SMALL: E <= EVAL_LDS_E, all
 // arrays in dynamic LDS, EVAL_PER_E + extra_per_e bytes per entity; else in the
 // handle's scratch, one block per workgroup) and by side; sets a.flags and
-// a.scratch.  pick(small, head) returns kernel<decltype(small)::value,
-// decltype(head)::value>.  prep() runs in the scratch regime only, once the
+// a.scratch.  pick(small, head, agg) returns kernel<decltype(small)::value,
+// decltype(head)::value, decltype(agg)::value>; agg is the handle's mode.  prep() runs in the scratch regime only, once the
 // scratch and m->eval_blocks exist: what else the kernel needs per workgroup.
 template <typename Args, typename Pick, typename Prep = NoPrep>
 int query_launch(rnnl_miner m, const char *who, int32_t side, int64_t n, size_t extra_per_e, Args &a,
@@ -248,9 +294,15 @@ int query_launch(rnnl_miner m, const char *who, int32_t side, int64_t n, size_t 
   if (n == 0) return RNNL_OK;
   a.flags = reinterpret_cast<unsigned long long *>(counters);
   const bool head = side == RNNL_MINER_HEAD;
+  auto kernel = [&](auto small) {  // the handle's mode and the side as template arguments
+    auto by_side = [&](auto agg) { return head ? pick(small, T(), agg) : pick(small, F(), agg); };
+    if (m->agg == AGG_NOISY_OR) return by_side(std::integral_constant<int, AGG_NOISY_OR>());
+    if (m->agg == AGG_MAX) return by_side(std::integral_constant<int, AGG_MAX>());
+    return by_side(std::integral_constant<int, AGG_SUM>());
+  };
   if (m->d.E <= EVAL_LDS_E) {
     const unsigned grid = (unsigned)std::min<int64_t>(n, EVAL_MAX_BLOCKS);
-    hipLaunchKernelGGL(head ? pick(T(), T()) : pick(T(), F()), dim3(grid), dim3(EB),
+    hipLaunchKernelGGL(kernel(T()), dim3(grid), dim3(EB),
                        (EVAL_PER_E + extra_per_e) * (size_t)m->d.E, st, m->d, m->l, a);
   } else {
     int rc = eval_scratch_ensure(m, who);
@@ -258,7 +310,7 @@ int query_launch(rnnl_miner m, const char *who, int32_t side, int64_t n, size_t 
     if (rc != RNNL_OK) return rc;
     a.scratch = m->eval_scratch;
     const unsigned grid = (unsigned)std::min<int64_t>(n, m->eval_blocks);
-    hipLaunchKernelGGL(head ? pick(F(), T()) : pick(F(), F()), dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
+    hipLaunchKernelGGL(kernel(F()), dim3(grid), dim3(EB), 0, st, m->d, m->l, a);
   }
   RNNL_HIP_CHECK(hipGetLastError());
   return RNNL_OK;

@@ -540,7 +540,7 @@ static int set_rules_impl(rnnl_miner m, const int32_t *rule_off, const int32_t *
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 4, &p_len);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 4 * RULE_STRIDE, &p_body);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 8, &p_prior);
-  if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 8 * 6, &p_state);
+  if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)n * 8 * 7, &p_state);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)m->ground_blocks * GROUND_PER_E * (size_t)E, &p_gs);
   if (rc == RNNL_OK) rc = dev_alloc(m, (size_t)R * 16 * (size_t)E, &p_cs);
   if (rc != RNNL_OK) {
@@ -556,7 +556,7 @@ static int set_rules_impl(rnnl_miner m, const int32_t *rule_off, const int32_t *
     else
       RNNL_HIP_CHECK(hipMemset(p_prior, 0, (size_t)n * 8));
   }
-  RNNL_HIP_CHECK(hipMemset(p_state, 0, std::max<size_t>((size_t)n * 8 * 6, 8)));
+  RNNL_HIP_CHECK(hipMemset(p_state, 0, std::max<size_t>((size_t)n * 8 * 7, 8)));
   RNNL_HIP_CHECK(hipMemset(p_gs, 0, (size_t)m->ground_blocks * GROUND_PER_E * (size_t)E));
   m->l.rule_off = static_cast<const int32_t *>(p_off);
   m->l.rule_len = static_cast<const int32_t *>(p_len);
@@ -569,6 +569,8 @@ static int set_rules_impl(rnnl_miner m, const int32_t *rule_off, const int32_t *
   m->l.at = st + 3 * (size_t)n;
   m->l.H = st + 4 * (size_t)n;
   m->l.val = st + 5 * (size_t)n;
+  m->l.op = st + 6 * (size_t)n;
+  m->agg = RNNL_MINER_AGG_SUM;  // (agg_depth is 1 again with the fresh MinerLearnDev)
   m->ground_scratch = static_cast<unsigned char *>(p_gs);
   m->chain_scratch = static_cast<unsigned char *>(p_cs);
   return RNNL_OK;

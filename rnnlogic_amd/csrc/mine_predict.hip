@@ -51,6 +51,14 @@
 // with `anc` the end the grounding starts at and `ans` the answer's end;
 // everything from eligibility on reads as on the tail side.
 //
+// The aggregation: the third template parameter AGG of both
+// kernels.  Under AGG_NOISY_OR / AGG_MAX val is built from the rules' operands
+// (mine_ground.h) and is still an ordinary non-negative double, so nothing
+// from eligibility on changes.  explain_kernel reads 1, not a path count,
+// where a rule arrives: a rule's contribution is its operand l.op[k], total
+// adds it in list order (noisy-or) or inserts it into the key (max), the
+// listed rules are those with the largest operand and every count is 1.
+//
 // LDS, EVAL_LDS_E = 512 entities: 52 KiB of eval_kernel's arrays + the list
 // (2 KiB) + 512 flag bytes + the histogram, the sort buffer and counters
 // (4.1 KiB): 58.6 KiB, under 64 KiB.
@@ -114,7 +122,7 @@ __device__ __forceinline__ bool query_bad(int anc, int r, int ans, int E, int R)
 
 enum : int { C_TOUCHED, C_ELIG, C_AHEAD, C_SURV, C_KNOWN, C_KNOWN_LT, C_TOUCHED_LT, C_CAND, C_N };
 
-template <bool SMALL, bool HEAD>
+template <bool SMALL, bool HEAD, int AGG>
 __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l, PredArgs a) {
   __shared__ int s_n[EW], s_na[EW];
   __shared__ unsigned int s_hist[256], s_wtot[EW], s_sel[3];
@@ -167,8 +175,8 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
 #pragma unroll 1
     for (int jb = 0; jb < nr; jb += EW) {
       const int nw = min(EW, nr - jb);  // rules of this round
-      eval_ground_round<HEAD>(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
-      eval_round_into_val<true>(l, ints, E, rb, jb, nw, s_na, val, flg, cand, &s_cnt[C_TOUCHED], wide);
+      eval_ground_round<HEAD, AGG>(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
+      eval_round_into_val<true, AGG>(l, ints, E, rb, jb, nw, s_na, val, flg, cand, &s_cnt[C_TOUCHED], wide);
     }
     if (wide) atomicOr(&a.flags[CTR_RANGE], 1ull);
     __syncthreads();
@@ -392,7 +400,7 @@ __global__ __launch_bounds__(EB) void predict_kernel(MinerDev d, MinerLearnDev l
   }
 }
 
-template <bool SMALL, bool HEAD>
+template <bool SMALL, bool HEAD, int AGG>
 __global__ __launch_bounds__(EB) void explain_kernel(MinerDev d, MinerLearnDev l, ExplArgs a) {
   __shared__ int s_n[EW], s_na[EW];
   const int E = d.E, tid = threadIdx.x;
@@ -431,7 +439,7 @@ __global__ __launch_bounds__(EB) void explain_kernel(MinerDev d, MinerLearnDev l
 #pragma unroll 1
     for (int jb = 0; jb < nr; jb += EW) {
       const int nw = min(EW, nr - jb);  // rules of this round
-      eval_ground_round<HEAD>(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
+      eval_ground_round<HEAD, AGG>(d, l, ints, h, r, t, rb, jb, nw, s_n, s_na, wide);
       for (int w = 0; w < nw; ++w) {  // the round's rules one after the other: list order per slot
         const int len2 = l.rule_len[rb + jb + w];
         if (len2 == 0) continue;  // an empty body reaches nothing
@@ -439,11 +447,17 @@ __global__ __launch_bounds__(EB) void explain_kernel(MinerDev d, MinerLearnDev l
         if (ent >= 0) {
           const unsigned long long c = ld_u64(&f.ca[ent]);  // 0 wherever the rule does not arrive
           if (c > 0) {
-            const double term = l.wt[rb + jb + w] * (double)c;
-            tot = tot + term;
+            // the contribution: wt * count (sum); the rule's operand, u_k or its class (noisy-or, max; c is 1)
+            const double term = AGG == AGG_SUM ? l.wt[rb + jb + w] * (double)c : l.op[rb + jb + w];
+            if (AGG != AGG_MAX)
+              tot = tot + term;
+            else if (term > 0.0)
+              tot = agg_max_insert(tot, (unsigned)term, l.agg_depth);
             ++nf;
             int pos = nl;  // behind every listed rule that contributes at least as much
-            while (pos > 0 && l.wt[rb + rl[pos - 1]] * (double)(unsigned long long)cl[pos - 1] < term) --pos;
+            while (pos > 0 && (AGG == AGG_SUM ? l.wt[rb + rl[pos - 1]] * (double)(unsigned long long)cl[pos - 1]
+                                              : l.op[rb + rl[pos - 1]]) < term)
+              --pos;
             if (pos < a.c) {
               for (int j = min(nl, a.c - 1); j > pos; --j) {
                 rl[j] = rl[j - 1];
@@ -516,7 +530,9 @@ int rnnl_miner_predict_side(rnnl_miner m, int32_t side, const int32_t *queries, 
   a.position = position;
   return query_launch(
       m, "rnnl_miner_predict", side, n, PRED_PER_E, a, counters, stream,
-      [](auto small, auto head) { return predict_kernel<decltype(small)::value, decltype(head)::value>; },
+      [](auto small, auto head, auto agg) {
+        return predict_kernel<decltype(small)::value, decltype(head)::value, decltype(agg)::value>;
+      },
       [&]() {  // the lists and flags of the scratch's workgroups, in a buffer of their own
         if (!m->pred_flags) {
           void *p = nullptr;
@@ -571,9 +587,10 @@ int rnnl_miner_explain_side(rnnl_miner m, int32_t side, const int32_t *queries, 
   a.total = total;
   a.rule = rule;
   a.count = reinterpret_cast<long long *>(count);
-  return query_launch(m, "rnnl_miner_explain", side, n, 0, a, counters, stream, [](auto small, auto head) {
-    return explain_kernel<decltype(small)::value, decltype(head)::value>;
-  });
+  return query_launch(m, "rnnl_miner_explain", side, n, 0, a, counters, stream,
+                      [](auto small, auto head, auto agg) {
+                        return explain_kernel<decltype(small)::value, decltype(head)::value, decltype(agg)::value>;
+                      });
 }
 
 int rnnl_miner_explain(rnnl_miner m, const int32_t *queries, int64_t n, const int32_t *index, int32_t n_slots,

@@ -27,6 +27,10 @@ running mean (RuleGenerator::update) and the rule file (out_rules)
     miner.predict_topk(queries, k=10, side="head")     # (h, r, t), h = -1 open: the first k heads of (?, r, t);
     miner.scores / eval_ranks / explain / predict(..., side="head")   # every call above on the head side
 
+    miner.set_aggregation("noisy_or")   # or ("max", depth=1..3): how every query call above combines the rules that
+    miner.set_weights(miner.confidence("pca"))         # reach an entity; weights are then confidences
+    miner.score_value(score, r)         # a score as the value to show: the probability / the strongest rule's weight
+
     miner.rule_stats()                  # dict(support, body, pca_body): int64 per rule of the current lists (or of
     miner.pool_stats()                  # rel2rules given) / of the searched pool, in get_logic_rules() order
     miner.head_pairs(); miner.confidence("pca" | "std" | "head_coverage", pc=0.0)
@@ -42,6 +46,8 @@ running mean (RuleGenerator::update) and the rule file (out_rules)
     python -m rnnlogic_amd.miner -data-path D -rule-file F -evaluate test -side both   # tails, heads, both: a line each
     python -m rnnlogic_amd.miner -data-path D -rule-file F -predict test -side head -predictions-file P
     python -m rnnlogic_amd.miner ... -side head -queries-file Q -predictions-file P    # [head]<TAB>relation<TAB>tail
+    python -m rnnlogic_amd.miner -data-path D -rule-file F -weights conf -agg noisy-or -evaluate test
+    python -m rnnlogic_amd.miner ... -weights conf -conf pca -agg max -agg-depth 2 -predict test -predictions-file P
 
 The pool equals the reference's for the same train graph: every relation
 path of length <= max_length from h to t of a train triple (h, r, t), the
@@ -78,6 +84,12 @@ tails by val descending, then entity id, among the entities some rule reaches
 rules with a path to it, their counts and the ones that contribute most.  The
 top k are selected inside the workgroup that built val, so the (n, |E|)
 matrix of `scores` is never written.
+
+set_aggregation replaces the sum in all of these by the two
+aggregations that belong to confidences: noisy-or, val[e] = sum of
+-log1p(-w_k) over the rules that reach e, and max, val[e] = a key of the
+strongest (and, at depth 2 and 3, next strongest) rules that reach e.  Both ask
+only whether a rule reaches an entity, so no path count can pass 32 bits.
 
 side="head" answers (?, r, t) with the same rules: val[e] =
 sum_k wt[k] * #paths(e -> t along body k), grounded backward from t over the
@@ -357,6 +369,87 @@ def keep_rules(support, conf, min_support=0, min_confidence=0.0):
     return (np.asarray(support) >= min_support) & (np.asarray(conf) >= min_confidence)
 
 
+AGGREGATIONS = ("sum", "noisy_or", "max")
+MAX_CLASSES = _native.MINER_AGG_CLASS_MAX  # 131,071: three 17-bit classes fit the 51 bits of a max key
+_NOISY_OR_CAP = 1.0 - 2.0 ** -53           # the largest double below 1: a confidence of 1 stays finite
+
+
+def _per_relation_weights(weights):
+    return [np.asarray(w, dtype=np.float64).reshape(-1) for w in weights]
+
+
+def noisy_or_operand(weights):
+    """weights[r][k] in [0, 1] (confidences, one sequence per relation) -> per
+    relation the float64 array u_k = -log1p(-min(w_k, 1 - 2^-53)): the operand
+    of the noisy-or aggregation, whose score is the sum of u_k over the firing
+    rules = -log prod(1 - w_k).  Each element is math.log1p's (the C
+    library's), so a plain Python restatement reproduces it bitwise whatever
+    vector path numpy's own log1p takes.  A weight outside [0, 1] (or NaN) is a
+    ValueError naming relation and rule index."""
+    out = []
+    for r, w in enumerate(_per_relation_weights(weights)):
+        bad = np.flatnonzero(~((w >= 0.0) & (w <= 1.0)))
+        if len(bad):
+            raise ValueError("noisy_or: the weight %r of rule %d of relation %d is not in [0, 1]"
+                             % (float(w[bad[0]]), int(bad[0]), r))
+        out.append(np.asarray([-math.log1p(-min(x, _NOISY_OR_CAP)) for x in w.tolist()], dtype=np.float64))
+    return out
+
+
+def max_classes(weights):
+    """weights[r][k] finite and >= 0 -> (classes, values): per relation the
+    int64 class of each rule and the ascending distinct positive weights.
+    values[r][c - 1] is the weight of class c = 1..C; equal weights share a
+    class; a weight of 0 has class 0, which contributes nothing.  A negative or
+    non-finite weight, or more than 131,071 classes in a relation, is a
+    ValueError naming the relation (and the rule index)."""
+    classes, values = [], []
+    for r, w in enumerate(_per_relation_weights(weights)):
+        bad = np.flatnonzero(~((w >= 0.0) & np.isfinite(w)))
+        if len(bad):
+            raise ValueError("max: the weight %r of rule %d of relation %d is not finite and >= 0"
+                             % (float(w[bad[0]]), int(bad[0]), r))
+        vals = np.unique(w[w > 0.0])
+        if len(vals) > MAX_CLASSES:
+            raise ValueError("max: relation %d has %d distinct positive weights, more than the %d classes a key holds"
+                             % (r, len(vals), MAX_CLASSES))
+        cls = np.where(w > 0.0, np.searchsorted(vals, w) + 1, 0).astype(np.int64)
+        classes.append(cls)
+        values.append(vals)
+    return classes, values
+
+
+def decode_max(score, values):
+    """A max score (the key c1 * 2^34 + c2 * 2^17 + c3 as a double) and the
+    relation's `values` of max_classes -> an array (..., 3) of the weights of
+    the strongest, second and third strongest firing rule, 0.0 for an empty
+    position.  A score that is no key of these classes is a ValueError."""
+    s = np.asarray(score, dtype=np.float64)
+    table = np.concatenate([[0.0], np.asarray(values, dtype=np.float64).reshape(-1)])
+    if not np.all((s >= 0.0) & (s < 2.0 ** 51) & (np.floor(s) == s)):
+        raise ValueError("decode_max: a score is not a max key (an integer in [0, 2^51))")
+    k = s.astype(np.uint64)
+    c = np.stack([k >> np.uint64(34), (k >> np.uint64(17)) & np.uint64(0x1FFFF), k & np.uint64(0x1FFFF)],
+                 -1).astype(np.int64)
+    if c.size and int(c.max()) >= len(table):
+        raise ValueError("decode_max: class %d in a score, the relation has %d" % (int(c.max()), len(table) - 1))
+    return table[c]
+
+
+def noisy_or_probability(score):
+    """The probability 1 - prod(1 - w_k) behind a noisy-or score: -expm1(-score)."""
+    return -np.expm1(-np.asarray(score, dtype=np.float64))
+
+
+def _check_agg(agg, depth, what="set_aggregation"):
+    agg = {"noisy-or": "noisy_or"}.get(agg, agg)
+    if agg not in AGGREGATIONS:
+        raise ValueError("%s: agg must be 'sum', 'noisy_or' or 'max' (got %r)" % (what, agg))
+    if isinstance(depth, bool) or int(depth) != depth or not 1 <= int(depth) <= 3:
+        raise ValueError("%s: depth must be 1, 2 or 3 (got %r)" % (what, depth))
+    return agg, int(depth)
+
+
 def stats_line(head, body, x, support, body_size, pca_body, std, pca):
     return "%d%s %.16f %d %d %d %.16f %.16f\n" % (head, "".join(" %d" % b for b in body), x, support, body_size,
                                                   pca_body, std, pca)
@@ -364,6 +457,7 @@ def stats_line(head, body, x, support, body_size, pca_body, std, pca):
 
 class RuleMiner(object):
     max_body = 3  # the longest rule body search / set_logic_rules / read_rules / mine take; 3..5 per miner
+    _agg, _agg_depth, _agg_stale, _agg_values, _rules_set = "sum", 1, False, None, False  # set_aggregation
 
     def __init__(self, graph, device=None, max_body=3):
         self.graph = graph
@@ -393,6 +487,10 @@ class RuleMiner(object):
         self._rule_body = np.zeros((0, 3), dtype=np.int32)
         self._pool_stats = None       # pool_stats() of the searched pool, until the next search
         self._head_pairs = None
+        self._agg, self._agg_depth = "sum", 1   # set_aggregation: sticky over new rules and weights
+        self._agg_stale = False       # the handle's mode / operand no longer follow the current rules and weights
+        self._agg_values = None       # max: per relation the ascending distinct positive weights (decode_max)
+        self._rules_set = False
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -506,6 +604,7 @@ class RuleMiner(object):
         body = np.ascontiguousarray(body, dtype=np.int32)
         pr = np.ascontiguousarray(prior, dtype=np.float64)
         self._rule_len, self._rule_body = ln, body
+        self._rules_set = self._agg_stale = True  # (the native call puts the handle back to the sum)
         entry = "rnnl_miner_set_rules" if body.shape[1] == 3 else "rnnl_miner_set_rules_long"  # n x 3 / n x 5
         with torch.cuda.device(self.device):
             _native.call(entry, self._handle, self._rule_off.ctypes.data, ln.ctypes.data, body.ctypes.data,
@@ -594,6 +693,7 @@ class RuleMiner(object):
         triples; drawn from the miner's seeded generator if absent)."""
         order, n_used = self._use_order(order if order is not None else self._rng.permutation(len(self._hrt)),
                                         portion)
+        self._agg_stale = True  # the weights move
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             for begin, count, pb, n_pairs, pair_off, dst, cnt, odev in self._chunks(order, n_used):
@@ -746,11 +846,72 @@ class RuleMiner(object):
         """rel2weights[r][k] (float64) becomes the weight of rule k of relation
         r's current list; the rules' Adam state is cleared, H stays."""
         flat = flatten_weights(self._rule_off, rel2weights)
+        self._agg_stale = True
         with torch.cuda.device(self.device):
             dev = torch.from_numpy(flat).to(self.device)
             _native.call("rnnl_miner_set_weights", self._handle, dev.data_ptr(),
                          torch.cuda.current_stream(self.device).cuda_stream)
             torch.cuda.current_stream(self.device).synchronize()  # dev is released on return
+
+    # ----------------------------------------------------------- aggregation
+    def set_aggregation(self, agg="sum", depth=1):
+        """How scores / eval_ranks / evaluate / predict_topk / explain / predict
+        combine the rules that reach an entity.  'sum' (the
+        default, the reference's): weight * path count, summed.  'noisy_or':
+        weights are confidences in [0, 1]; the score is the sum of -log1p(-w)
+        over the firing rules, which ranks as 1 - prod(1 - w) does.  'max':
+        weights finite and >= 0; the score is a key of the `depth` (1..3)
+        strongest firing rules — depth 1 the plain max, 2 and 3 break its ties
+        by the next strongest (decode_max reads the key).  Sticky: it survives
+        set_logic_rules, set_weights, read_rules, learn and mine; the operand
+        is derived from weights() again before the next query, and a weight the
+        mode does not admit raises ValueError there, before any kernel runs.
+        learn, h_score and the statistics never look at it."""
+        self._agg, self._agg_depth = _check_agg(agg, depth)
+        self._agg_stale = True
+
+    @property
+    def aggregation(self):
+        """(agg, depth) as set_aggregation took them; depth is 1 unless agg is 'max'."""
+        return self._agg, (self._agg_depth if self._agg == "max" else 1)
+
+    def _sync_aggregation(self):
+        """Before a query launch: the handle's mode and operand follow the
+        current rules, weights and set_aggregation."""
+        if not self._agg_stale or not self._rules_set:
+            return  # (without rules the query itself is refused)
+        code, operand, values = _native.MINER_AGG_SUM, None, None
+        if self._agg == "noisy_or":
+            code, operand = _native.MINER_AGG_NOISY_OR, noisy_or_operand(self.weights())
+        elif self._agg == "max":
+            classes, values = max_classes(self.weights())
+            code, operand = _native.MINER_AGG_MAX, [c.astype(np.float64) for c in classes]
+        with torch.cuda.device(self.device):
+            dev = None
+            if operand is not None:
+                flat = np.concatenate(operand + [np.zeros(0, dtype=np.float64)])
+                dev = torch.from_numpy(np.ascontiguousarray(flat, dtype=np.float64)).to(self.device)
+            _native.call("rnnl_miner_set_aggregation", self._handle, code, self._agg_depth,
+                         dev.data_ptr() if dev is not None else None,
+                         torch.cuda.current_stream(self.device).cuda_stream)  # (synchronises: dev may go)
+        self._agg_values = values
+        self._agg_stale = False
+
+    def score_value(self, score, r):
+        """A score of relation r's queries as the value to show: the score
+        itself ('sum'), the probability 1 - prod(1 - w) ('noisy_or'), the
+        weight of the strongest firing rule ('max'; 0.0 if none).  Scores that
+        are not finite (-inf past `valid`) stay as they are."""
+        s = np.asarray(score, dtype=np.float64)
+        if self._agg == "sum":
+            return s
+        fin = np.isfinite(s)
+        if self._agg == "noisy_or":
+            return np.where(fin, noisy_or_probability(np.where(fin, s, 0.0)), s)
+        self._sync_aggregation()
+        if self._agg_values is None:
+            raise RuntimeError("RuleMiner.score_value: set the rules and weights first")
+        return np.where(fin, decode_max(np.where(fin, s, 0.0), self._agg_values[int(r)])[..., 0], s)
 
     def read_rules(self, file_name):
         """Sets the rules of a 'head body... x' file (out_rules /
@@ -794,6 +955,7 @@ class RuleMiner(object):
         _check_side(side, "RuleMiner")
         q = self._queries(triples)
         n, E = len(q), self.graph.entity_size
+        self._sync_aggregation()
         with torch.cuda.device(self.device):
             qd = torch.from_numpy(q).to(self.device)
             ranks = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
@@ -807,7 +969,11 @@ class RuleMiner(object):
         """(n, |E|) float64 on the device: per query (h, r, t) the val of every
         entity — sum over r's rules of weight * path count from h, the triple's
         own edge removed — bitwise what the reference computes.  side 'head':
-        weight * path count from the entity to t, the same edge removed."""
+        weight * path count from the entity to t, the same edge removed.
+        After set_aggregation('noisy_or'): the sum of -log1p(-weight) over the
+        rules with a path (noisy_or_probability gives the probability); after
+        set_aggregation('max', depth): the key of the depth strongest such
+        rules (decode_max gives their weights); +0.0 where no rule arrives."""
         return self._evaluate(triples, False, True, side)[1]
 
     def eval_ranks(self, triples, filtered=True, side="tail"):
@@ -874,7 +1040,10 @@ class RuleMiner(object):
         eligible order (also past k), -1 if t is not eligible or the query is
         open.  side 'head': the first k heads of (?, r, t) by the head-side
         score; queries (n, 3) (h, r, t), h = -1 open; the other known heads of
-        (r, t) leave, h stays; position is the place of h."""
+        (r, t) leave, h stays; position is the place of h.  The order and the
+        scores are those of the aggregation set (set_aggregation): the noisy-or
+        sum or the max key in place of the weighted path count; score_value
+        turns a score into the value to show."""
         k = int(k)
         if not 1 <= k <= _native.MINER_TOPK_MAX:
             raise ValueError("predict_topk: k must be 1..%d (got %d)" % (_native.MINER_TOPK_MAX, k))
@@ -882,6 +1051,7 @@ class RuleMiner(object):
             raise ValueError("predict_topk: candidates must be 'reached' or 'all' (got %r)" % (candidates,))
         q = self._pred_queries(queries, side)
         n = len(q)
+        self._sync_aggregation()
         with torch.cuda.device(self.device):
             qd = torch.from_numpy(q).to(self.device)
             index = torch.empty((n, k), dtype=torch.int32, device=self.device)
@@ -904,12 +1074,18 @@ class RuleMiner(object):
         rules_per_tail (1..16) rules with the largest weight * count, ties by
         list index, as indices into the relation's rule list (-1 unused), and
         count (n, m, c) int64 = their path counts.  side 'head': the entities
-        are heads of (?, r, t), the paths run from the entity to t."""
+        are heads of (?, r, t), the paths run from the entity to t.  After
+        set_aggregation('noisy_or' / 'max'): fired as before; total = the
+        entity's score bitwise (the sum of -log1p(-weight) in list order / the
+        key of all firing rules at the depth set); rule = the firing rules by
+        weight descending, ties by list index; count = 1 for each of them (the
+        paths are not counted, so no count can pass 32 bits)."""
         c = int(rules_per_tail)
         if not 1 <= c <= _native.MINER_EXPLAIN_MAX:
             raise ValueError("explain: rules_per_tail must be 1..%d (got %d)" % (_native.MINER_EXPLAIN_MAX, c))
         q = self._pred_queries(queries, side)
         n = len(q)
+        self._sync_aggregation()
         with torch.cuda.device(self.device):
             idx = torch.as_tensor(index, device=self.device).to(torch.int32).contiguous()
             if idx.dim() != 2 or idx.shape[0] != n or not 1 <= idx.shape[1] <= _native.MINER_TOPK_MAX:
@@ -934,7 +1110,7 @@ class RuleMiner(object):
         and, with explain = m > 0, explain_fired / explain_total (n, m') and
         explain_rule / explain_count (n, m', rules_per_tail) of the first m' =
         min(m, k) places (`explain`).  output: one TSV line per prediction —
-        head, relation, place (1-based), tail, repr(score), `*` on the known
+        head, relation, place (1-based), tail, repr(score_value(score)), `*` on the known
         answer, then for the explained places `head <- b1, b2:count:weight`
         per listed rule, names from the graph's dictionaries.  side 'head':
         the heads of (?, r, t); the lines keep the triple's orientation —
@@ -982,7 +1158,7 @@ class RuleMiner(object):
                     e = int(out["index"][i, j])
                     cols = [_name(self.graph, "id2entity", e if head else h), _name(self.graph, "id2relation", r),
                             "h%d" % (j + 1) if head else str(j + 1), _name(self.graph, "id2entity", t if head else e),
-                            repr(float(out["score"][i, j])), "*" if e == (h if head else t) else ""]
+                            repr(float(self.score_value(out["score"][i, j], r))), "*" if e == (h if head else t) else ""]
                     if j < m:
                         cols += [self.rule_text(r, kk, c, wt[r][kk]) for kk, c in
                                  zip(out["explain_rule"][i, j].tolist(), out["explain_count"][i, j].tolist())
@@ -1157,6 +1333,9 @@ def main(argv=None):
     ap.add_argument("-rules-per-tail", dest="rules_per_tail", type=int, default=3)
     ap.add_argument("-candidates", dest="candidates", choices=["reached", "all"], default="reached")
     ap.add_argument("-side", dest="side", choices=["tail", "head", "both"], default="tail")
+    ap.add_argument("-agg", dest="agg", choices=["sum", "noisy-or", "max"], default="sum")
+    ap.add_argument("-agg-depth", dest="agg_depth", type=int, default=1)
+    ap.add_argument("-weights", dest="weights", choices=["file", "conf"], default="file")
     a = ap.parse_args(argv)
     predicting = a.predict is not None or a.queries_file is not None
     if a.output_file is None and a.rule_file is None:
@@ -1180,6 +1359,12 @@ def main(argv=None):
         ap.error("-pc and -min-support must be >= 0")
     if a.rule_file is not None and (a.min_support or a.min_conf or a.prior is not None or a.prior_weight):
         ap.error("-min-support, -min-conf, -prior and -prior-weight belong to mining, not to -rule-file")
+    if not 1 <= a.agg_depth <= 3:
+        ap.error("-agg-depth must be 1..3")
+    if a.agg_depth != 1 and a.agg != "max":
+        ap.error("-agg-depth belongs to -agg max")
+    if (a.agg != "sum" or a.weights != "file") and a.evaluate is None and not predicting:
+        ap.error("-agg and -weights act on -evaluate, -predict and -queries-file: give one of them")
     # mining: bodies as long as asked for; a rule file: as long as the miner holds
     miner = RuleMiner(KnowledgeGraph(a.data_path),
                       max_body=MAX_BODY if a.rule_file is not None else max(3, a.max_length))
@@ -1196,6 +1381,14 @@ def main(argv=None):
         print("#Rules read: %d" % miner.read_rules(a.rule_file))
         if a.stats_file is not None:
             print("#Rule statistics written: %d" % miner.write_list_stats(a.stats_file, a.pc))
+    if a.weights == "conf":  # the confidences of the current lists become their weights
+        miner.set_weights(miner.confidence(a.conf, a.pc))
+    if a.agg != "sum":
+        miner.set_aggregation(a.agg, a.agg_depth)
+        try:
+            miner._sync_aggregation()
+        except ValueError as err:
+            ap.error("-agg %s: %s (-weights conf takes the rules' confidences as weights)" % (a.agg, err))
     for split in {None: (), "both": ("valid", "test")}.get(a.evaluate, (a.evaluate,)):
         if a.side == "tail":
             print(metrics_line(split.capitalize(), miner.evaluate(split)))
