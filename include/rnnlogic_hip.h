@@ -848,6 +848,51 @@ int rnnl_miner_explain_side(rnnl_miner m, int32_t side, const int32_t *queries, 
 #define RNNL_MINER_AGG_CLASS_MAX 131071
 int rnnl_miner_set_aggregation(rnnl_miner m, int32_t agg, int32_t depth, const double *operand, void *stream);
 
+/* ---------------------------------- the grounding paths behind an answer --
+ * rnnl_miner_paths_side lists, per query, slot and rule, the first paths of the
+ * count that rnnl_miner_explain* reports.  queries, side, index (n x n_slots)
+ * as for rnnl_miner_explain_side; rule (device, n x n_slots x c int32) names
+ * per slot up to c rules of relation r's list by their index, -1 an unused
+ * entry.  Any rule of the list may be named, whether or not rnnl_miner_explain
+ * listed it.
+ *   A path of rule r <- b_1..b_L (1 <= L <= 5) is a sequence of train edges
+ *   x_0 -b_1-> x_1 ... -b_L-> x_L with x_0 = h and x_L = the slot's entity e
+ *   (RNNL_MINER_TAIL), or x_0 = e and x_L = t (RNNL_MINER_HEAD); every copy of
+ *   the query's own edge (h, r, t) is skipped on every hop, an open query skips
+ *   nothing.  A train triple that is in the graph twice is two edges: a path
+ *   through it counts twice and is listed twice, in adjacent places.
+ *   Order: by the entities read from e back toward the query's anchor: tail
+ *   side x_{L-1} ascending, then x_{L-2}, ...; head side x_1, then x_2, ....
+ *   Per (query, slot, entry):
+ *     count (n x n_slots x c int64): the exact number of paths, the count of
+ *       rnnl_miner_explain under RNNL_MINER_AGG_SUM; 0 where the rule does not
+ *       fire at e;
+ *     listed (n x n_slots x c int32): min(max_paths, count);
+ *     path (n x n_slots x c x max_paths x RNNL_MINER_PATH_LEN int32): the
+ *       first `listed` paths in that order, each as x_0 .. x_L in the triple's
+ *       orientation, -1 past x_L and in the rows past `listed`.
+ *   An unused slot or entry (-1), and a rule without a body, give count 0,
+ *   listed 0 and -1 throughout.  A rule index outside the relation's list or an
+ *   entity out of range sets counters[2] and counts as unused.
+ *   Paths are always counted: the aggregation of the handle
+ *   (rnnl_miner_set_aggregation) changes nothing here and stays as set.
+ *   counters (device, 4 x uint64, zeroed here): [1] != 0: a path count of a
+ *   named rule does not fit u32 (RNNL_ERR_RANGE for the caller to raise, as
+ *   from rnnl_miner_explain), [2] as above or a query out of range, [3]:
+ *   internal.  No float, no atomics on the outputs: two calls are equal byte
+ *   for byte.
+ * 1 <= max_paths <= RNNL_MINER_PATHS_MAX; n_slots and c as for
+ * rnnl_miner_explain; n * n_slots * c * max_paths * RNNL_MINER_PATH_LEN must be
+ * below 2^31.  These, a null handle, rules not set, an unknown side or a null
+ * array are RNNL_ERR_INVALID with a message, decided before any device call.
+ * Scratch for graphs of more than 512 entities is the handle's: one call per
+ * handle at a time.  Asynchronous on `stream`. */
+#define RNNL_MINER_PATHS_MAX 64
+#define RNNL_MINER_PATH_LEN 6
+int rnnl_miner_paths_side(rnnl_miner m, int32_t side, const int32_t *queries, int64_t n, const int32_t *index,
+                          int32_t n_slots, const int32_t *rule, int32_t c, int32_t max_paths, int32_t *listed,
+                          int64_t *count, int32_t *path, uint64_t *counters, void *stream);
+
 /* ------------------------------------- support and confidence of rules --
  * The exact counts behind standard and PCA confidence, on the handle's train
  * graph as given: no inverses, and — unlike search, learn and evaluate — no

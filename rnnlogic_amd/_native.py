@@ -22,6 +22,7 @@ ERR_COUNT_WIDTH, ERR_NODE_RANGE, ERR_ACC_RANGE = 8, 16, 32
 TOPK_MAX = 1024  # RNNL_TOPK_MAX
 KGE_TAIL, KGE_HEAD = 0, 1
 MINER_TOPK_MAX, MINER_EXPLAIN_MAX = 256, 16  # RNNL_MINER_TOPK_MAX, RNNL_MINER_EXPLAIN_MAX
+MINER_PATHS_MAX, MINER_PATH_LEN = 64, 6  # RNNL_MINER_PATHS_MAX, RNNL_MINER_PATH_LEN
 MINER_REACHED, MINER_ALL = 0, 1
 MINER_TAIL, MINER_HEAD = 0, 1  # RNNL_MINER_TAIL, RNNL_MINER_HEAD
 MINER_AGG_SUM, MINER_AGG_NOISY_OR, MINER_AGG_MAX = 0, 1, 2  # RNNL_MINER_AGG_*
@@ -129,6 +130,7 @@ SIGNATURES = [
      [_P, _I32, _P, _I64, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     ("rnnl_miner_explain_side", ctypes.c_int, [_P, _I32, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     ("rnnl_miner_set_aggregation", ctypes.c_int, [_P, _I32, _I32, _P, _P]),
+    ("rnnl_miner_paths_side", ctypes.c_int, [_P, _I32, _P, _I64, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     ("rnnl_miner_rule_stats_scratch", ctypes.c_int, [_P, _I64, _I64, _I32, _P]),
     ("rnnl_miner_rule_stats", ctypes.c_int,
      [_P, _I64, _P, _P, _P, _P, _I32, ctypes.c_uint32, _P, ctypes.c_size_t, _P, _P, _P]),

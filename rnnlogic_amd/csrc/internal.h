@@ -124,6 +124,8 @@ struct rnnl_miner_s {
   int32_t eval_blocks = 0;
   // rnnl_miner_predict above its LDS regime: per workgroup a list (int) and a flag byte per entity; one of bufs
   unsigned char *pred_flags = nullptr;
+  // rnnl_miner_paths_side above its LDS regime: per workgroup the kept levels of one grounding; one of bufs
+  unsigned char *path_scratch = nullptr;
   // how evaluate / predict / explain form val (rnnl_miner_set_aggregation); set_rules puts it back to SUM
   int32_t agg = 0;
 };

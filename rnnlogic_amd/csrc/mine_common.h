@@ -1,6 +1,6 @@
 // What every kernel file of the rule miner shares (mine.hip, mine_learn.hip,
-// mine_stats.hip and, through mine_ground.h, mine_eval.hip and
-// mine_predict.hip): the counter slots, the search in a sorted int array, the
+// mine_stats.hip and, through mine_ground.h, mine_eval.hip, mine_predict.hip
+// and mine_paths.hip): the counter slots, the search in a sorted int array, the
 // relaxed u64 load, and the path-count grounding of mine_learn.hip and
 // mine_ground.h: its scratch block and its hop.  One copy of each, so what
 // scores() grounds is what learn() grounds, hop for hop.

@@ -22,6 +22,8 @@ running mean (RuleGenerator::update) and the rule file (out_rules)
     miner.predict_topk(queries, k=10)   # (h, r) or (h, r, t) -> device index, score, valid, position (filtered top-k)
     miner.explain(queries, index, 3)    # per listed tail: fired, total, the 3 rules that contribute most, their counts
     miner.predict("test", k=10, explain=3, output="pred.tsv")   # both, as numpy arrays and as a TSV file
+    miner.explain_paths(queries, index, rule, 3)       # per listed rule: its first 3 grounding paths, their exact count
+    miner.predict("test", k=10, explain=3, paths=2, output="pred.tsv")  # ... `rule:count:weight [a > x > b | ...]`
 
     miner.evaluate("test", side="both") # the two-sided protocol: tail pairs then head pairs, n = 2 x triples
     miner.predict_topk(queries, k=10, side="head")     # (h, r, t), h = -1 open: the first k heads of (?, r, t);
@@ -43,6 +45,7 @@ running mean (RuleGenerator::update) and the rule file (out_rules)
     python -m rnnlogic_amd.miner -data-path D -rule-file F -evaluate test        # evaluate a rule file, no mining
     python -m rnnlogic_amd.miner -data-path D -rule-file F -predict test -predictions-file P -k 10 -explain 3
     python -m rnnlogic_amd.miner -data-path D -rule-file F -queries-file Q -predictions-file P   # head<TAB>relation[<TAB>tail]
+    python -m rnnlogic_amd.miner ... -predict test -explain 3 -paths 2 -predictions-file P    # + the paths behind each rule
     python -m rnnlogic_amd.miner -data-path D -rule-file F -evaluate test -side both   # tails, heads, both: a line each
     python -m rnnlogic_amd.miner -data-path D -rule-file F -predict test -side head -predictions-file P
     python -m rnnlogic_amd.miner ... -side head -queries-file Q -predictions-file P    # [head]<TAB>relation<TAB>tail
@@ -84,6 +87,12 @@ tails by val descending, then entity id, among the entities some rule reaches
 rules with a path to it, their counts and the ones that contribute most.  The
 top k are selected inside the workgroup that built val, so the (n, |E|)
 matrix of `scores` is never written.
+
+explain_paths (rnnl_miner_paths_side, csrc/mine_paths.hip) shows
+the paths a count stands for: per (query, listed entity, rule) the exact number
+of grounding paths and the first few of them as entity sequences, ordered by
+their entities read from the listed entity back toward the query's anchor.  It
+counts paths whatever aggregation is set.
 
 set_aggregation replaces the sum in all of these by the two
 aggregations that belong to confidences: noisy-or, val[e] = sum of
@@ -367,6 +376,12 @@ def confidences(kind, support, body, pca_body, head_pairs, pc=0.0):
 def keep_rules(support, conf, min_support=0, min_confidence=0.0):
     """The filter of best_rules / out_rules: True where a rule stays."""
     return (np.asarray(support) >= min_support) & (np.asarray(conf) >= min_confidence)
+
+
+def path_text(path_row, graph=None):
+    """One row of explain_paths' `path` (x_0 .. x_L, -1 past x_L) as `a > x > b`:
+    entity names from the graph's dictionary, the ids themselves without a graph."""
+    return " > ".join(_name(graph, "id2entity", int(x)) for x in path_row if int(x) >= 0)
 
 
 AGGREGATIONS = ("sum", "noisy_or", "max")
@@ -1101,8 +1116,58 @@ class RuleMiner(object):
                           fired.data_ptr(), total.data_ptr(), rule.data_ptr(), count.data_ptr())
         return fired, total, rule, count
 
+    @torch.no_grad()
+    def explain_paths(self, queries, index, rule, max_paths=3, side="tail"):
+        """The grounding paths behind rules of listed entities
+        (rnnl_miner_paths_side).  queries and index (n, m) as for
+        `explain`; rule (n, m, c) int32, c <= 16: per slot indices into the
+        relation's rule list, -1 unused — what `explain` returned, or any other
+        rules of the list.  A path of rule r <- b1..bL is x_0 -b1-> x_1 ...
+        -bL-> x_L over train edges, from the query's h to the entity (side
+        'tail') or from the entity to the query's t (side 'head'), every copy
+        of the query's own edge skipped; a triple that is in train twice gives
+        two edges and so two equal paths.  Returns device tensors: listed
+        (n, m, c) int32 = min(max_paths, count), count (n, m, c) int64 = the
+        exact number of paths (`explain`'s count under 'sum'; 0 where the rule
+        does not fire), path (n, m, c, max_paths, 6) int32 = the first `listed`
+        paths as x_0 .. x_L, -1 past x_L and in unlisted rows.  Order: by the
+        entities read from the listed entity back toward the anchor — tail
+        side x_{L-1} ascending, then x_{L-2}, ...; head side x_1, then x_2, ....
+        Paths are counted whatever set_aggregation says.  max_paths 1..64."""
+        P = int(max_paths)
+        if not 1 <= P <= _native.MINER_PATHS_MAX:
+            raise ValueError("explain_paths: max_paths must be 1..%d (got %d)" % (_native.MINER_PATHS_MAX, P))
+        q = self._pred_queries(queries, side)
+        n = len(q)
+        ishape = tuple(index.shape) if hasattr(index, "shape") else np.shape(index)
+        if len(ishape) != 2 or ishape[0] != n or not 1 <= ishape[1] <= _native.MINER_TOPK_MAX:
+            raise ValueError("explain_paths: index must be (n, m) with 1 <= m <= %d (got %r for %d queries)"
+                             % (_native.MINER_TOPK_MAX, ishape, n))
+        m = ishape[1]
+        rshape = tuple(rule.shape) if hasattr(rule, "shape") else np.shape(rule)
+        if len(rshape) != 3 or rshape[:2] != (n, m) or not 1 <= rshape[2] <= _native.MINER_EXPLAIN_MAX:
+            raise ValueError("explain_paths: rule must be (n, m, c) with 1 <= c <= %d (got %r for index %r)"
+                             % (_native.MINER_EXPLAIN_MAX, rshape, ishape))
+        c = rshape[2]
+        if n * m * c * P * _native.MINER_PATH_LEN >= 2 ** 31:
+            raise ValueError("explain_paths: path would have 2^31 elements or more (cut the queries into smaller calls)")
+        with torch.cuda.device(self.device):
+            idx = torch.as_tensor(index, device=self.device).to(torch.int32).contiguous()
+            rl = torch.as_tensor(rule, device=self.device).to(torch.int32).contiguous()
+            qd = torch.from_numpy(q).to(self.device)
+            listed = torch.empty((n, m, c), dtype=torch.int32, device=self.device)
+            count = torch.empty((n, m, c), dtype=torch.int64, device=self.device)
+            path = torch.empty((n, m, c, P, _native.MINER_PATH_LEN), dtype=torch.int32, device=self.device)
+            self._counted("rnnl_miner_paths_side", _side_code(side), qd.data_ptr(), n, idx.data_ptr(), m,
+                          rl.data_ptr(), c, P, listed.data_ptr(), count.data_ptr(), path.data_ptr())
+        return listed, count, path
+
+    def path_text(self, path_row):
+        """A row of explain_paths' `path` in the entity names of the graph: `a > x > b`."""
+        return path_text(path_row, self.graph)
+
     def predict(self, split="test", triples=None, k=10, filtered=True, explain=0, rules_per_tail=3,
-                candidates="reached", output=None, side="tail"):
+                candidates="reached", output=None, side="tail", paths=0):
         """The miner's answers on graph.valid_facts / test_facts (split
         'valid' / 'test') or the given queries ((n, 2) or (n, 3), as
         predict_topk), with the current rules and weights.  Returns a dict of
@@ -1115,8 +1180,18 @@ class RuleMiner(object):
         per listed rule, names from the graph's dictionaries.  side 'head':
         the heads of (?, r, t); the lines keep the triple's orientation —
         predicted head, relation, place written h1, h2, ..., the query's tail,
-        score, `*`, rules."""
+        score, `*`, rules.  paths = P > 0 (with explain > 0): explain_paths of
+        the explained places and their listed rules as explain_paths_listed /
+        explain_paths_count (n, m', rules_per_tail) and explain_path (n, m',
+        rules_per_tail, P, 6); in the file each rule column becomes
+        `head <- b1, b2:count:weight [a > x > b | a > y > b]`, ` | ...` appended
+        inside the brackets where there are more paths than are listed."""
         _check_side(side, "predict")
+        P = int(paths)
+        if P and not 1 <= P <= _native.MINER_PATHS_MAX:
+            raise ValueError("predict: paths must be 0..%d (got %d)" % (_native.MINER_PATHS_MAX, P))
+        if P and min(int(explain), int(k)) <= 0:
+            raise ValueError("predict: paths lists the paths of explained rules: give explain > 0 with it")
         if triples is None:
             if split not in ("valid", "test"):
                 raise ValueError("predict: split must be 'valid' or 'test'")
@@ -1129,13 +1204,20 @@ class RuleMiner(object):
         m = min(int(explain), int(k))
         if m > 0:
             names = ("explain_fired", "explain_total", "explain_rule", "explain_count")
+            pnames = ("explain_paths_listed", "explain_paths_count", "explain_path")
             if len(q):
                 got = self.explain(q, index[:, :m].contiguous(), rules_per_tail, side)
                 out.update((name, v.cpu().numpy()) for name, v in zip(names, got))
+                if P:
+                    out.update((name, v.cpu().numpy()) for name, v in
+                               zip(pnames, self.explain_paths(q, index[:, :m].contiguous(), got[2], P, side)))
             else:
                 c = int(rules_per_tail)
                 out.update(zip(names, (np.zeros((0, m), np.int32), np.zeros((0, m), np.float64),
                                        np.zeros((0, m, c), np.int32), np.zeros((0, m, c), np.int64))))
+                if P:
+                    out.update(zip(pnames, (np.zeros((0, m, c), np.int32), np.zeros((0, m, c), np.int64),
+                                            np.zeros((0, m, c, P, _native.MINER_PATH_LEN), np.int32))))
         if output is not None:
             self._write_predictions(output, out, m, side)
         return out
@@ -1148,9 +1230,16 @@ class RuleMiner(object):
                              ", ".join(_name(self.graph, "id2relation", b) for b in body))
         return text if count is None else "%s:%d:%r" % (text, count, float(weight))
 
+    def paths_text(self, rows, listed, count):
+        """The bracket behind a rule column: the `listed` first rows of one (P, 6)
+        block of explain_paths' `path`, ` | ...` where `count` says there are more."""
+        parts = [self.path_text(row) for row in rows[:int(listed)]]
+        return "[%s]" % " | ".join(parts + (["..."] if int(count) > int(listed) else []))
+
     def _write_predictions(self, path, out, m, side="tail"):
         wt = self.weights() if m > 0 else None
         head = side == "head"
+        with_paths = m > 0 and "explain_path" in out
         with open(path, "w") as fo:
             for i in range(len(out["h"])):
                 h, r, t = int(out["h"][i]), int(out["r"][i]), int(out["t"][i])
@@ -1159,10 +1248,17 @@ class RuleMiner(object):
                     cols = [_name(self.graph, "id2entity", e if head else h), _name(self.graph, "id2relation", r),
                             "h%d" % (j + 1) if head else str(j + 1), _name(self.graph, "id2entity", t if head else e),
                             repr(float(self.score_value(out["score"][i, j], r))), "*" if e == (h if head else t) else ""]
-                    if j < m:
+                    if j < m and not with_paths:
                         cols += [self.rule_text(r, kk, c, wt[r][kk]) for kk, c in
                                  zip(out["explain_rule"][i, j].tolist(), out["explain_count"][i, j].tolist())
                                  if kk >= 0]
+                    elif j < m:
+                        cols += ["%s %s" % (self.rule_text(r, kk, c, wt[r][kk]),
+                                            self.paths_text(out["explain_path"][i, j, s],
+                                                            out["explain_paths_listed"][i, j, s],
+                                                            out["explain_paths_count"][i, j, s]))
+                                 for s, (kk, c) in enumerate(zip(out["explain_rule"][i, j].tolist(),
+                                                                 out["explain_count"][i, j].tolist())) if kk >= 0]
                     fo.write("\t".join(cols) + "\n")
         return int(np.sum(out["valid"]))
 
@@ -1331,6 +1427,7 @@ def main(argv=None):
     ap.add_argument("-k", dest="k", type=int, default=10)
     ap.add_argument("-explain", dest="explain", type=int, default=0)
     ap.add_argument("-rules-per-tail", dest="rules_per_tail", type=int, default=3)
+    ap.add_argument("-paths", dest="paths", type=int, default=0)
     ap.add_argument("-candidates", dest="candidates", choices=["reached", "all"], default="reached")
     ap.add_argument("-side", dest="side", choices=["tail", "head", "both"], default="tail")
     ap.add_argument("-agg", dest="agg", choices=["sum", "noisy-or", "max"], default="sum")
@@ -1353,6 +1450,12 @@ def main(argv=None):
         ap.error("-k must be 1..%d" % _native.MINER_TOPK_MAX)
     if predicting and (a.explain < 0 or not 1 <= a.rules_per_tail <= _native.MINER_EXPLAIN_MAX):
         ap.error("-explain must be >= 0 and -rules-per-tail 1..%d" % _native.MINER_EXPLAIN_MAX)
+    if a.paths and not predicting:
+        ap.error("-paths acts on -predict and -queries-file: give one of them")
+    if predicting and not 0 <= a.paths <= _native.MINER_PATHS_MAX:
+        ap.error("-paths must be 0..%d" % _native.MINER_PATHS_MAX)
+    if predicting and a.paths and a.explain < 1:
+        ap.error("-paths lists the paths of explained rules: give -explain with it")
     if a.rule_file is None and not 1 <= a.max_length <= MAX_BODY:
         ap.error("-max-length must be 1..%d" % MAX_BODY)
     if a.pc < 0.0 or a.min_support < 0:
@@ -1398,7 +1501,7 @@ def main(argv=None):
                                miner.evaluate(split, side=side)))
     if predicting:
         out = miner.predict(a.predict, queries, a.k, True, a.explain, a.rules_per_tail, a.candidates,
-                            a.predictions_file, a.side)
+                            a.predictions_file, a.side, a.paths)
         print("#Predictions written: %d" % int(np.sum(out["valid"])))
 
 
