@@ -1038,6 +1038,62 @@ int rnnl_ground_wide(rnnl_graph g, rnnl_rules r, const int64_t *all_h, const int
                      uint64_t *out_count, int64_t cap, uint64_t *cursor, void *stream);
 int rnnl_forward_error_bits(void *workspace, void *stream, uint32_t *bits);
 
+/* ------------------------- the grounding paths behind a predicted tail --
+ * rnnl_paths_rows lists, for rows of a forward, the paths that a rule's count at
+ * an entity stands for.  It works on the graph and rules handles of the
+ * predictors (no miner handle, no second copy of the graph).
+ *   Row i is (all_h[i], all_r[i]) with optionally edges_to_remove[i], as in every
+ *   forward; the rows of one call may hold different relations.  entity (device,
+ *   n_rows x m int32) names one entity per slot, rule (device, n_rows x m x c
+ *   int32) per slot up to c rules by their global id: the index into the rules
+ *   as rnnl_rules_create read them.  The named rule must be all_r[i] <- b_1..b_L
+ *   with 1 <= L <= 5.
+ *   A path is a sequence of graph edges x_0 -b_1-> x_1 ... -b_L-> x_L with
+ *   x_0 = all_h[i] and x_L = entity[i][j].
+ *   Edge removal: with edges_to_remove (nullable; an entry < 0 removes nothing),
+ *   the edge with relation-local id edges_to_remove[i] of relation all_r[i] (the
+ *   ids of rnnl_graph_create's edge tables) is skipped on every hop whose
+ *   relation is all_r[i].  Its inverse-relation twin is a different edge and is
+ *   walked.  Without edges_to_remove nothing is skipped.
+ *   Duplicates: an edge that rnnl_graph_create was given twice is two edges; a
+ *   path through it counts twice and is listed twice, in adjacent places.  (The
+ *   removed id takes one of the copies away.  The forward's grounding kernel
+ *   resolves the id to its (source, target) and skips every copy, so the two
+ *   differ only on a graph with doubled triples, which KnowledgeGraph refuses.)
+ *   Order: the tail-side order of rnnl_miner_paths_side: paths are compared by
+ *   x_{L-1} ascending, then x_{L-2}, and so on.
+ *   Per (row, slot, entry):
+ *     count (n_rows x m x c int64): the exact number of paths, counted in u64
+ *       level by level (no error at 32 bits): the count the grounding COO holds
+ *       for that rule's trie node at that entity, rnnl_ground_wide's past 2^32;
+ *     listed (n_rows x m x c int32): min(max_paths, count);
+ *     path (n_rows x m x c x max_paths x RNNL_PATH_LEN int32): the first
+ *       `listed` paths as x_0 .. x_L, -1 past x_L and in the rows past `listed`.
+ *   A -1 slot, a -1 entry and a rule that does not reach the entity give 0, 0 and
+ *   -1 throughout.  counters (device, 4 x uint64, zeroed here): [2] != 0: an
+ *   entity or a rule id out of range, a rule whose head is not all_r[i], a body
+ *   longer than 5 or empty (such an entry counts as unused), or a row whose head,
+ *   relation or removed edge id is out of range (all its entries are unused);
+ *   [1] != 0: a level count carried out of 64 bits (RNNL_ERR_RANGE for the caller
+ *   to raise); [3]: internal.  No float, no atomics on the outputs, each element
+ *   written by one thread: two calls are equal byte for byte.
+ * scratch is the caller's (rnnl_paths_rows_scratch bytes for the same graph and
+ * n_rows: 0 for graphs of up to 512 entities, where it may be null; 8-byte
+ * aligned; its contents do not matter), so two streams or threads may call at
+ * once with a scratch each.
+ * m >= 1, 1 <= c <= 16, 1 <= max_paths <= RNNL_PATHS_MAX, n_rows >= 0, n_rows *
+ * m * c * max_paths * RNNL_PATH_LEN below 2^31; these, a null handle, rules of
+ * another graph, a null array or a scratch that is too small are
+ * RNNL_ERR_INVALID with a message, decided before any device call.
+ * Asynchronous on `stream`. */
+#define RNNL_PATHS_MAX 64
+#define RNNL_PATH_LEN 6
+int rnnl_paths_rows_scratch(rnnl_graph g, int32_t n_rows, size_t *bytes);
+int rnnl_paths_rows(rnnl_graph g, rnnl_rules r, const int64_t *all_h, const int64_t *all_r,
+                    const int64_t *edges_to_remove /* nullable */, int32_t n_rows, const int32_t *entity, int32_t m,
+                    const int32_t *rule, int32_t c, int32_t max_paths, int32_t *listed, int64_t *count, int32_t *path,
+                    void *scratch, size_t scratch_bytes, uint64_t *counters, void *stream);
+
 /* ------------------------------------------- RotatE embedding training --
  * The sampled-negative training step of RotatE tables (the model that wrote
  * the shipped RotatE_<dim> directories): eemb (n_entities x 2 dim, [re | im]),

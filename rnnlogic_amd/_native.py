@@ -23,6 +23,7 @@ TOPK_MAX = 1024  # RNNL_TOPK_MAX
 KGE_TAIL, KGE_HEAD = 0, 1
 MINER_TOPK_MAX, MINER_EXPLAIN_MAX = 256, 16  # RNNL_MINER_TOPK_MAX, RNNL_MINER_EXPLAIN_MAX
 MINER_PATHS_MAX, MINER_PATH_LEN = 64, 6  # RNNL_MINER_PATHS_MAX, RNNL_MINER_PATH_LEN
+PATHS_MAX, PATH_LEN = 64, 6  # RNNL_PATHS_MAX, RNNL_PATH_LEN
 MINER_REACHED, MINER_ALL = 0, 1
 MINER_TAIL, MINER_HEAD = 0, 1  # RNNL_MINER_TAIL, RNNL_MINER_HEAD
 MINER_AGG_SUM, MINER_AGG_NOISY_OR, MINER_AGG_MAX = 0, 1, 2  # RNNL_MINER_AGG_*
@@ -151,6 +152,9 @@ SIGNATURES = [
     ("rnnl_ground_wide", ctypes.c_int,
      [_P, _P, _P, _P, _P, _P, _I32, _P, ctypes.c_size_t, _P, _P, _P, _P, _I64, _P, _P]),
     ("rnnl_forward_error_bits", ctypes.c_int, [_P, _P, _P]),
+    ("rnnl_paths_rows_scratch", ctypes.c_int, [_P, _I32, ctypes.POINTER(ctypes.c_size_t)]),
+    ("rnnl_paths_rows", ctypes.c_int,
+     [_P, _P, _P, _P, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P, ctypes.c_size_t, _P, _P]),
     ("rnnl_predictorplus_backward_size", ctypes.c_int, [_P, _I32, _P]),
     ("rnnl_predictorplus_backward_rows_size", ctypes.c_int, [_I32, _I64, _P]),
     ("rnnl_pna_features", ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P,

@@ -32,6 +32,50 @@ static int upload(const std::vector<T> &h, void **slot, const T **dst) {
   return RNNL_OK;
 }
 
+// The in-edge view (GraphDev in_*): the edges sorted by (target, relation, source), the copies of one triple in
+// edge-id order.  Least significant key first: the edges laid out relation-major in id order (the order of edge_src /
+// edge_dst), then three stable counting passes, by source, by relation and by target.
+void build_in_edges(const int32_t *hrt, int64_t n, int32_t E, int32_t R, std::vector<int32_t> &in_off,
+                    std::vector<int32_t> &in_rel, std::vector<int32_t> &in_src, std::vector<int32_t> &in_eid) {
+  in_off.assign((size_t)E + 1, 0);
+  in_rel.assign((size_t)n, 0);
+  in_src.assign((size_t)n, 0);
+  in_eid.assign((size_t)n, 0);
+  // relation-major, relation-local id order: position ebase[r] + id
+  std::vector<int32_t> ebase((size_t)R + 1, 0), by_rel((size_t)n);
+  for (int64_t i = 0; i < n; ++i) ebase[hrt[3 * i + 1] + 1]++;
+  for (int r = 0; r < R; ++r) ebase[r + 1] += ebase[r];
+  {
+    std::vector<int32_t> fill(ebase.begin(), ebase.end() - 1);
+    for (int64_t i = 0; i < n; ++i) by_rel[fill[hrt[3 * i + 1]]++] = (int32_t)i;
+  }
+  // stable by source
+  std::vector<int32_t> cnt((size_t)E + 1, 0), by_src((size_t)n);
+  for (int64_t i = 0; i < n; ++i) cnt[hrt[3 * i] + 1]++;
+  for (int v = 0; v < E; ++v) cnt[v + 1] += cnt[v];
+  for (int64_t k = 0; k < n; ++k) by_src[cnt[hrt[3 * (int64_t)by_rel[k]]]++] = (int32_t)k;  // k: position in by_rel
+  // stable by relation, then (below) by target
+  std::vector<int32_t> by_sr((size_t)n);
+  {
+    std::vector<int32_t> fill(ebase.begin(), ebase.end() - 1);
+    for (int64_t j = 0; j < n; ++j) {
+      const int32_t k = by_src[j];
+      by_sr[fill[hrt[3 * (int64_t)by_rel[k] + 1]]++] = k;
+    }
+  }
+  for (int64_t i = 0; i < n; ++i) in_off[hrt[3 * i + 2] + 1]++;
+  for (int v = 0; v < E; ++v) in_off[v + 1] += in_off[v];
+  std::vector<int32_t> fill(in_off.begin(), in_off.end() - 1);
+  for (int64_t j = 0; j < n; ++j) {
+    const int32_t k = by_sr[j];
+    const int64_t i = by_rel[k];
+    const int32_t r = hrt[3 * i + 1], at = fill[hrt[3 * i + 2]]++;
+    in_rel[at] = r;
+    in_src[at] = hrt[3 * i];
+    in_eid[at] = k - ebase[r];
+  }
+}
+
 }  // namespace rnnl
 
 using namespace rnnl;
@@ -93,6 +137,8 @@ int rnnl_graph_create(const int32_t *hrt, int64_t n, int32_t E, int32_t R, rnnl_
     }
     dvoff.push_back(off[(v + 1) * R]);  // end of v's edges: the last present relation's end
   }
+  std::vector<int32_t> in_off, in_rel, in_src, in_eid;
+  build_in_edges(hrt, n, E, R, in_off, in_rel, in_src, in_eid);
   auto *g = new rnnl_graph_s;
   (void)hipGetDevice(&g->device);
   g->d.E = E;
@@ -103,7 +149,9 @@ int rnnl_graph_create(const int32_t *hrt, int64_t n, int32_t E, int32_t R, rnnl_
   if ((rc = upload(off, &g->mem[0], &g->d.off)) || (rc = upload(col, &g->mem[1], &g->d.col)) ||
       (rc = upload(ebase, &g->mem[2], &g->d.edge_base)) || (rc = upload(esrc, &g->mem[3], &g->d.edge_src)) ||
       (rc = upload(edst, &g->mem[4], &g->d.edge_dst)) || (rc = upload(vbits, &g->mem[5], &g->d.vbits)) ||
-      (rc = upload(dvoff, &g->mem[6], &g->d.dvoff))) {
+      (rc = upload(dvoff, &g->mem[6], &g->d.dvoff)) || (rc = upload(in_off, &g->mem[7], &g->d.in_off)) ||
+      (rc = upload(in_rel, &g->mem[8], &g->d.in_rel)) || (rc = upload(in_src, &g->mem[9], &g->d.in_src)) ||
+      (rc = upload(in_eid, &g->mem[10], &g->d.in_eid))) {
     rnnl_graph_destroy(g);
     return rc;
   }
@@ -302,7 +350,9 @@ int rnnl_rules_create(rnnl_graph g, const int32_t *tok, const int64_t *ptr, int3
       (rc = upload(node_info, &rs->mem[13], &node_info_dev)) ||
       (rc = upload(node_parent, &rs->mem[14], &rs->d.node_parent)) ||
       (rc = upload(node_tok, &rs->mem[15], &rs->d.node_tok)) ||
-      (rc = upload(level_nodes, &rs->mem[16], &rs->d.level_nodes))) {
+      (rc = upload(level_nodes, &rs->mem[16], &rs->d.level_nodes)) ||
+      (rc = upload(rs->node_of_rule, &rs->mem[17], &rs->d.rule_node)) ||
+      (rc = upload(node_depth, &rs->mem[18], &rs->d.node_depth))) {
     rnnl_rules_destroy(rs);
     return rc;
   }

@@ -29,6 +29,13 @@ struct GraphDev {
   const int32_t *edge_base = nullptr;  // R + 1: start of relation r's edge table
   const int32_t *edge_src = nullptr;   // relation-major, relation-local file order
   const int32_t *edge_dst = nullptr;
+  // in-edge view (rnnl_paths_rows, paths.hip): the edges into t are [in_off[t], in_off[t + 1]), sorted by
+  // (relation, source), copies of one triple by edge id; in_eid is the edge's relation-local id (edge_src's index
+  // minus edge_base[relation]).  No E*R table: a relation's run is found by binary search in in_rel.
+  const int32_t *in_off = nullptr;  // E + 1
+  const int32_t *in_rel = nullptr;  // n_edges
+  const int32_t *in_src = nullptr;  // n_edges
+  const int32_t *in_eid = nullptr;  // n_edges
 };
 
 // Rule miner graph (mine.hip): out-edges grouped by source, in-edges grouped
@@ -90,6 +97,10 @@ struct RulesDev {
   const int32_t *node_parent = nullptr;
   const int32_t *node_tok = nullptr;
   const int32_t *level_nodes = nullptr;
+  // rnnl_paths_rows: the trie node where each rule's body ends (the host's node_of_rule) and each node's depth
+  // (the length of the body that ends there)
+  const int32_t *rule_node = nullptr;   // n_rules
+  const int32_t *node_depth = nullptr;  // n_nodes
 };
 
 // Node-weight records (bytes per node); see rnnl_node_weights.
@@ -99,6 +110,11 @@ constexpr int kStridePna = 256;  // int32 fix(sum x)[16] | int32 fix(sum x^2)[16
                                  // (one shift per table and column: trailer[1], trailer[4])
 
 void set_error(const std::string &msg);
+
+// The in-edge view of GraphDev from the triples (n x 3: h r t, checked by the caller to be in range): a plain host
+// function, vectors out (graph.cpp; tests/asan/in_edges_check.cpp checks it on its own).
+void build_in_edges(const int32_t *hrt, int64_t n, int32_t E, int32_t R, std::vector<int32_t> &in_off,
+                    std::vector<int32_t> &in_rel, std::vector<int32_t> &in_src, std::vector<int32_t> &in_eid);
 
 // The SUM node records' fixed-point pass (node_fix_kernel, ground.hip) over
 // every node of the table (rnnl_lstm_encode_trie_sum's last launch).
@@ -133,7 +149,7 @@ struct rnnl_miner_s {
 struct rnnl_graph_s {
   rnnl::GraphDev d;
   int device = 0;
-  void *mem[7] = {};
+  void *mem[11] = {};
 };
 
 struct rnnl_rules_s {

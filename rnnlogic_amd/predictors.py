@@ -509,6 +509,101 @@ class _HipGrounding(object):
             torch.cumsum(torch.bincount(slot, minlength=n * m), 0, out=off[1:])
         return off, (torch.cat(rules) if rules else empty), (torch.cat(counts) if counts else empty)
 
+    @torch.no_grad()
+    @_native.on_input_device
+    def explain_paths(self, all_h, all_r, entities, rules, max_paths=3, edges_to_remove=None):
+        """The grounding paths behind rules at predicted tails (rnnl_paths_rows,
+        DESIGN §3.20).  Rows as for explain_rows; entities (n, m) names one
+        entity per slot, rules (n, m, c), c <= 16, per slot rule ids in
+        explain_rows' numbering (the rules as set_rules read them); -1 is an
+        unused slot or entry.  A path of rule all_r[i] <- b1..bL (1 <= L <= 5)
+        is x_0 -b1-> x_1 ... -bL-> x_L over graph edges from all_h[i] to the
+        slot's entity; with edges_to_remove the row's own edge is skipped on
+        every hop of its relation (its inverse twin is walked).  Returns device
+        tensors: listed (n, m, c) int32 = min(max_paths, count), count
+        (n, m, c) int64 = the exact number of paths (explain_rows' count, also
+        past 2^32; 0 where the rule does not reach the entity), path
+        (n, m, c, max_paths, 6) int32 = the first `listed` paths as x_0 .. x_L,
+        -1 past x_L and in unlisted rows.  Order: by the entities read from the
+        slot's entity back toward all_h[i] — x_{L-1} ascending, then x_{L-2},
+        ... (RuleMiner.explain_paths' tail side).  An entity or rule id out of
+        range, a rule of another relation than the row's, a body without or
+        with more than five relations: ValueError after the call.
+        max_paths 1..64."""
+        P = int(max_paths)
+        if not 1 <= P <= _native.PATHS_MAX:
+            raise ValueError("explain_paths: max_paths must be 1..%d (got %d)" % (_native.PATHS_MAX, P))
+        device, all_h, all_r, etr = self._rows(all_h, all_r, edges_to_remove)
+        n = all_h.numel()
+        eshape = tuple(entities.shape) if hasattr(entities, "shape") else np.shape(entities)
+        if len(eshape) != 2 or eshape[0] != n or eshape[1] < 1:
+            raise ValueError("explain_paths: entities must be (n, m) with m >= 1 (got %r for %d rows)" % (eshape, n))
+        m = eshape[1]
+        rshape = tuple(rules.shape) if hasattr(rules, "shape") else np.shape(rules)
+        if len(rshape) != 3 or rshape[:2] != (n, m) or not 1 <= rshape[2] <= 16:
+            raise ValueError("explain_paths: rules must be (n, m, c) with 1 <= c <= 16 (got %r for entities %r)"
+                             % (rshape, eshape))
+        c = rshape[2]
+        if n * m * c * P * _native.PATH_LEN >= 2 ** 31:
+            raise ValueError("explain_paths: path would have 2^31 elements or more (cut the rows into smaller calls)")
+        if etr is not None and etr.numel() != n:
+            raise ValueError("explain_paths: edges_to_remove must hold one edge id per row")
+        ent = torch.as_tensor(entities, device=device).to(torch.int32).contiguous()
+        rl = torch.as_tensor(rules, device=device).to(torch.int32).contiguous()
+        listed = torch.empty((n, m, c), dtype=torch.int32, device=device)
+        count = torch.empty((n, m, c), dtype=torch.int64, device=device)
+        path = torch.empty((n, m, c, P, _native.PATH_LEN), dtype=torch.int32, device=device)
+        if n == 0:
+            return listed, count, path
+        g, nr = self.graph.device_graph(device), self.native_rules(device)
+        need = ctypes.c_size_t()
+        _native.call("rnnl_paths_rows_scratch", g, n, ctypes.byref(need))
+        scratch = torch.empty(need.value, dtype=torch.uint8, device=device) if need.value else None
+        counters = torch.empty(4, dtype=torch.int64, device=device)
+        _native.call("rnnl_paths_rows", g, nr.ptr, all_h.data_ptr(), all_r.data_ptr(),
+                     etr.data_ptr() if etr is not None else None, n, ent.data_ptr(), m, rl.data_ptr(), c, P,
+                     listed.data_ptr(), count.data_ptr(), path.data_ptr(),
+                     scratch.data_ptr() if scratch is not None else None, need.value, counters.data_ptr(),
+                     torch.cuda.current_stream(device).cuda_stream)
+        flags = counters.cpu().tolist()  # (waits for the launch: the scratch is free after it)
+        if flags[3]:
+            raise _native.NativeError(_native.RNNL_ERR_INTERNAL, "explain_paths: the kernel's self-check failed")
+        if flags[1]:
+            raise _native.NativeError(_native.RNNL_ERR_RANGE, "explain_paths: a path count does not fit 64 bits")
+        if flags[2]:
+            raise ValueError("explain_paths: an entity, rule id, head or removed edge out of range, a rule of another "
+                             "relation than its row's, or a body that is empty or longer than five relations")
+        return listed, count, path
+
+    def top_rules(self, off, rule, count, m):
+        """Per slot of explain_rows' CSR the first m rules by (count descending,
+        rule id ascending): (rule (slots, m) int32, -1 where the slot lists
+        fewer).  On the device; the order of the predictions file's columns."""
+        device = off.device
+        slots = off.numel() - 1
+        out = torch.full((slots, m), -1, dtype=torch.int32, device=device)
+        if rule.numel() == 0:
+            return out
+        lens = off[1:] - off[:-1]
+        slot = torch.repeat_interleave(torch.arange(slots, device=device), lens)
+        # stable sorts, least significant key first: rule id, count descending, slot
+        order = torch.argsort(rule, stable=True)
+        order = order[torch.argsort(-count[order], stable=True)]
+        order = order[torch.argsort(slot[order], stable=True)]
+        place = torch.arange(order.numel(), device=device) - off[:-1][slot[order]]
+        keep = place < m
+        out[slot[order][keep], place[keep]] = rule[order][keep].to(torch.int32)
+        return out
+
+    def listable(self, named):
+        """Rule ids as explain_paths takes them: those of rules it cannot walk
+        (no body — such a rule reaches the head itself — or more than five
+        relations) set to -1, the others kept in place."""
+        if not len(self.rules):
+            return torch.full_like(named, -1)
+        ok = torch.tensor([1 <= len(body) <= 5 for _, body in self.rules], dtype=torch.bool, device=named.device)
+        return torch.where((named >= 0) & ok[named.clamp(min=0).long()], named, torch.full_like(named, -1))
+
 
 def topk_rows(score, mask, flag, keep, k):
     """rnnl_topk_rows on device tensors: score (n, E) f32, mask / flag (n, E)

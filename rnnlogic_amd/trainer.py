@@ -445,7 +445,7 @@ class TrainerPredictor(object):
 
     @torch.no_grad()
     @_native.on_self_device
-    def predict(self, split, k=10, filtered=True, explain=0, output=None):
+    def predict(self, split, k=10, filtered=True, explain=0, output=None, paths=0):
         """The model's answers on a split: for every row (h, r, t) the first k
         tails of (h, r, ?) by score (ties by entity id; rnnl_topk_rows), among
         the rule-reached candidates and, when `filtered`, without the other
@@ -460,7 +460,22 @@ class TrainerPredictor(object):
         explain_count of each row's first m predictions (explain_rows).
         output: rank 0 writes one TSV line per prediction — head, relation,
         rank (1-based), tail, score, `*` on the known answer, then up to m
-        `rule:count` pairs in relation names, the rules with most paths first."""
+        `rule:count` pairs in relation names, the rules with most paths first.
+        paths = P > 0 (with explain > 0): the grounding paths behind those
+        columns (explain_paths).  Per explained slot the rules
+        the file lists — the first m by (count descending, rule id ascending),
+        picked on the device — as explain_paths_rule (n, m, m) int32 (-1 where
+        fewer reach the tail), their explain_paths_listed / explain_paths_count
+        (n, m, m) and explain_path (n, m, m, P, 6); in the file each rule
+        column becomes `head <- b1, b2:count [a > x > b | a > y > b]`, ` | ...`
+        appended inside the brackets where there are more paths than listed.
+        A listed rule without a body (it reaches the head itself) or with more
+        than five relations has no path to walk: 0 listed, count 0, `[]`."""
+        P = int(paths)
+        if P and not 1 <= P <= _native.PATHS_MAX:
+            raise ValueError("predict: paths must be 0..%d (got %d)" % (_native.PATHS_MAX, P))
+        if P and min(int(explain), int(k)) <= 0:
+            raise ValueError("predict: paths lists the paths of explained rules: give explain > 0 with it")
         eval_set = getattr(self, "%s_set" % split)
         model = self.model
         model.eval()
@@ -478,6 +493,14 @@ class TrainerPredictor(object):
             off, rule, count = model.explain_rows(all_h, all_r, index[:, :m])
             out["explain_len"] = (off[1:] - off[:-1]).view(-1, m)  # per slot, so the ranks' CSRs concatenate
             out["explain_rule"], out["explain_count"] = rule, count
+            if P:
+                n = all_h.numel()
+                named = model.top_rules(off, rule, count, m).view(n, m, m)
+                # (a listed rule without a body, or with more than five relations, has no path to list: 0 / 0 / -1)
+                listed, pcount, path = model.explain_paths(all_h, all_r, index[:, :m].contiguous(),
+                                                           model.listable(named), P)
+                out["explain_paths_rule"], out["explain_paths_listed"] = named, listed
+                out["explain_paths_count"], out["explain_path"] = pcount, path
         if self.world_size > 1:
             out = comm.cat(out)
         out = {key: v.cpu().numpy() for key, v in out.items()}
@@ -492,6 +515,16 @@ class TrainerPredictor(object):
         graph = self.model.graph
         ent, rel = graph.id2entity, graph.id2relation
         rules = self.model.rules
+        with_paths = m > 0 and "explain_path" in out
+        if with_paths:
+            from .miner import path_text
+
+            def bracket(i, j, s):
+                """` [a > x > b | ...]`: the listed paths of rule column s of slot (i, j)."""
+                listed = int(out["explain_paths_listed"][i, j, s])
+                parts = [path_text(row, graph) for row in out["explain_path"][i, j, s][:listed]]
+                more = ["..."] if int(out["explain_paths_count"][i, j, s]) > listed else []
+                return " [%s]" % " | ".join(parts + more)
         with open(path, "w") as fo:
             for i in range(len(out["h"])):
                 h, r, t = int(out["h"][i]), int(out["r"][i]), int(out["t"][i])
@@ -503,7 +536,9 @@ class TrainerPredictor(object):
                         a, b = out["explain_off"][i * m + j], out["explain_off"][i * m + j + 1]
                         pairs = sorted(zip(out["explain_count"][a:b].tolist(), out["explain_rule"][a:b].tolist()),
                                        key=lambda cr: (-cr[0], cr[1]))[:m]
-                        cols += ["%s:%d" % (self.rule_text(rules[ri]), c) for c, ri in pairs]
+                        # (explain_paths_rule[i, j] holds these rules in this order)
+                        cols += ["%s:%d%s" % (self.rule_text(rules[ri]), c, bracket(i, j, s) if with_paths else "")
+                                 for s, (c, ri) in enumerate(pairs)]
                     fo.write("\t".join(cols) + "\n")
 
     # ------------------------------------------------------------------ checkpoints
